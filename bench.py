@@ -22,11 +22,16 @@ Every phase writes one marker line per rank to stderr and re-arms a watchdog (`-
 every thread's stack and exits 1 (class Progress); the reduction route (native RCCL or a torch.distributed callback) is agreed on by all
 ranks; `--gpus N` under a launcher with another WORLD_SIZE is refused.  `--dump-h PATH`: rank 0 saves the last Hessenberg matrix.
 
-Prints ONE JSON line on rank 0; `value` = Arnoldi iterations per second, whole job.
+A plain run sets up, warms up (`--warmup` factorisations), times `--steps` factorisations, writes the last one's outputs when
+`--dump-outputs DIR` is given (DIR/H.npy, info.npy, X_rows.npy: float64, the basis on a fixed, seeded sample of rows; see
+dump_outputs) and prints its line.  `--full` adds what the headline does not need: `cpu_baseline` (unless --no-cpu-baseline),
+`launch_bound_regime` and `config.parity` (H against the committed fixture of this workload; a failed check exits 4).
+
+Prints ONE JSON line on rank 0; `value` = Arnoldi iterations per second, whole job; `ms_per_step` = milliseconds per timed step.
   roofline   : the DGS sweep kernels (lk::panel_dot_cw for sweep 1, lk::panel_sweep for sweeps 2 and 3) -- algorithmic bytes s*n_local*(k+1|k+2)
                per launch (s*n*(3k+5) per DGS) / HIP-event duration on the kernel's
                stream, averaged over every sweep launch of the timed region; peak = 8 TB/s HBM3E.
-  cpu_baseline: the reference-schedule CPU oracle (oracle/, 1 thread, kind "port") timed on this
+  cpu_baseline (--full): the reference-schedule CPU oracle (oracle/, 1 thread, kind "port") timed on this
                host on a bounded sample and scaled to the metric's unit (see `sample`), the byte model
                checked on a second sample; plus an all-core leg running the engine's fused schedule.
 """
@@ -446,6 +451,49 @@ def _laplacian_csr_rows(N: int, row0: int, n_local: int):
     return rowptr, cols[ok].astype(np.int32), np.ascontiguousarray(vals[ok])
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs writes at most this much in all
+DUMP_ROWS_SEED = 20240917         # the fixed seed of the sampled basis rows
+
+
+def dump_outputs(out_dir: str, X, H: np.ndarray, info: int, n: int, row0: int, n_local: int, ctx, dist=None, rank: int = 0) -> None:
+    """--dump-outputs DIR: what a caller of lk_arnoldi receives from the last timed factorisation, as float64 .npy files --
+    H.npy (the (m+1) x m Hessenberg matrix), info.npy (the status, one element) and X_rows.npy (the Krylov basis on a fixed, seeded
+    sample of GLOBAL rows, ascending, all m+1 columns; the whole basis is n x (m+1), far beyond the budget).  Complex arrays carry a
+    trailing axis of 2 (real, imaginary).  The rows depend on (n, m, dtype) only, so two builds run with the same arguments write
+    files that compare element for element, whatever the number of ranks; every rank gathers its own rows of the sample, rank 0
+    writes."""
+    ncols = X.ncols
+    itemsize = X.dtype.itemsize
+    h_bytes = H.size * itemsize
+    if h_bytes + 64 > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs: H alone is {h_bytes} bytes, over the {DUMP_BUDGET_BYTES}-byte budget")
+    k = int(min(n, (DUMP_BUDGET_BYTES - h_bytes - 4096) // (ncols * itemsize), 16384))
+    rows = np.unique(np.random.default_rng(DUMP_ROWS_SEED).integers(0, n, size=k, dtype=np.int64))
+    mine = rows[(rows >= row0) & (rows < row0 + n_local)]
+    import torch
+    with ctx.torch_stream():
+        idx = torch.as_tensor(mine - row0, device=f"cuda:{ctx.device}")
+        block = torch.stack([X[j].as_torch("r")[idx] for j in range(ncols)], dim=1).cpu().numpy() if mine.size else \
+            np.zeros((0, ncols), dtype=X.dtype)
+    ctx.sync()
+    parts = [(mine, block)]
+    if dist is not None and dist.get_world_size() > 1:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (mine, block))
+    if rank != 0:
+        return
+    got = np.concatenate([p[0] for p in parts])
+    Xs = np.concatenate([p[1] for p in parts], axis=0)[np.argsort(got, kind="stable")]
+
+    def real(a: np.ndarray) -> np.ndarray:
+        a = np.ascontiguousarray(a)
+        return a.view(np.float64).reshape(a.shape + (2,)) if np.iscomplexobj(a) else a.astype(np.float64, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "H.npy"), real(H))
+    np.save(os.path.join(out_dir, "info.npy"), np.array([float(info)]))
+    np.save(os.path.join(out_dir, "X_rows.npy"), real(Xs))
+
+
 def main() -> None:
     if len(sys.argv) == 3 and sys.argv[1] == "--cpu-fused-leg":      # the child of cpu_baseline's all-core leg: host only, no torch, no GPU
         print(json.dumps(_fused_leg(*json.loads(sys.argv[2]))), flush=True)
@@ -478,7 +526,15 @@ def main() -> None:
     ap.add_argument("--dump-h", default=None, metavar="PATH", help="rank 0 saves the Hessenberg matrix of the last factorisation (.npy): parity checks of sharded runs")
     ap.add_argument("--no-profile", action="store_true",
                     help="diagnostic: leave the library's per-kernel HIP events off (value only; roofline fields are then zero)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (unless --no-cpu-baseline), the launch-bound "
+                         "context leg and the parity check of H against the committed fixture (a failed check ends the run with status 4)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/H.npy, DIR/info.npy and DIR/X_rows.npy "
+                         "(float64; the basis on a fixed, seeded sample of rows; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     parity_failed = False
 
     under_launcher = "WORLD_SIZE" in os.environ or "RANK" in os.environ
@@ -660,6 +716,9 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        progress.phase(f"writing the last factorisation's outputs to {args.dump_outputs}")
+        dump_outputs(args.dump_outputs, X, H, info, n, row0, n_local, ctx, dist, rank)
 
     n_sweeps, sweep_ms, sweep_bytes = ctx.profile_get("dgs_sweep*")
     n_dgs, dgs_ms, dgs_bytes = ctx.profile_get("dgs")
@@ -733,10 +792,11 @@ def main() -> None:
             attribution["other (finish kernels, normalise, launch gaps, host)"] = max(0.0, 1.0 - sum(attribution.values()))
         # self-check of the line: where the repository holds a fixture of the reference's arithmetic for exactly this workload (the
         # metric configuration and configs[1]), every column of the H just computed is compared with it -- whatever the number of
-        # ranks, so a scaling run whose reduction went wrong says so in its own line (the fixture is data, tests/golden/)
+        # ranks, so a scaling run whose reduction went wrong says so in its own line (the fixture is data, tests/golden/).  --full only:
+        # a plain run does what its headline figure needs (its outputs can be compared with --dump-outputs instead)
         parity = None
         fx = os.path.join(ROOT, "tests", "golden", f"arnoldi_diaglin_n{n}_m{m}_rdp.npz")
-        if args.operator == "diag" and args.dtype == "f64" and os.path.exists(fx):
+        if args.full and args.operator == "diag" and args.dtype == "f64" and os.path.exists(fx):
             try:
                 z = np.load(fx)
                 cerr = lambda Ha, Hb: float(max(np.abs(Ha[:, j] - Hb[:, j]).max() / np.abs(Hb[:, j]).max() for j in range(Hb.shape[1])))  # noqa: E731
@@ -820,14 +880,16 @@ def main() -> None:
             r["algorithmic_bytes_per_launch"] = mv_bytes_model
             r["bytes_priced"] = "ALGORITHMIC bytes of one operator application: s*n_local*n (the matrix) + s*(n + n_local) (x read, y written)"
             r["traffic"], r["traffic_source"] = None, "no PMC record for this workload"
-        if world == 1 and not args.no_cpu_baseline:
+        # the CPU baselines and the launch-bound context leg measure something else than the headline: --full only
+        cpu_legs = args.full and world == 1 and not args.no_cpu_baseline
+        if cpu_legs:
             progress.phase("cpu_baseline: the oracle on this host's cores (bounded samples)")
-        if world == 1 and not args.no_cpu_baseline and args.operator != "diag":
+        if cpu_legs and args.operator != "diag":
             try:
                 out["cpu_baseline"] = cpu_baseline_operator(args.operator, n, m)
             except Exception as exc:  # noqa: BLE001
                 out["cpu_baseline"] = {"value": None, "unit": "Arnoldi iterations/s", "cores": 1, "kind": "port", "sample": f"failed: {exc!r}"}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif cpu_legs:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, m, args.cpu_n, args.cpu_m, progress)
             except Exception as exc:  # noqa: BLE001
@@ -835,7 +897,7 @@ def main() -> None:
                                        "sample": f"failed: {exc!r}"}
         # (a context leg like cpu_baseline: --no-cpu-baseline drops it too -- the PMC / kernel-trace passes of tools/run_profiles_final.sh must see the
         #  metric workload's launches only, the small-n sweeps would land in the same kernel instantiations' averages)
-        if world == 1 and args.operator == "diag" and not args.shard_of and not args.no_cpu_baseline:
+        if cpu_legs and args.operator == "diag" and not args.shard_of:
             try:
                 out["launch_bound_regime"] = launch_bound_regime(ctx)
             except Exception as exc:  # noqa: BLE001 - context only: never costs the metric line

@@ -181,7 +181,7 @@ def test_config5_at_full_size_as_eight_processes_against_the_oracle_fixture(tmp_
     import numpy as np
     z = np.load(os.path.join(ROOT, "tests", "golden", "arnoldi_diaglin_n100000000_m128_rdp.npz"))
     hpath = str(tmp_path / "H8.npy")
-    out = _run([sys.executable, "bench.py", "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dump-h", hpath],
+    out = _run([sys.executable, "bench.py", "--gpus", "8", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--dump-h", hpath],
                LK_DIST_BACKEND="gloo", LK_FORCE_DEVICE="0")
     assert out["n_gpus"] == 8 and out["config"]["n_local"] == 12_500_000 and out["config"]["m"] == 128 and out["config"]["info"] == 0
     H = np.load(hpath)
@@ -212,7 +212,7 @@ def test_a_wrong_reduction_ends_the_run_nonzero_with_its_line_printed():
     """The line polices itself: one rank's partial sums scaled by 1 + 1e-6 before every all-reduce (test hook, callback route) -- the
     factorisation still runs to the end and the line is printed, with config.parity.ok = false against the committed fixture, and EVERY
     rank leaves with a non-zero status.  The same command without the fault: ok = true, status 0."""
-    args = ["--gpus", "2", "--rows", "10000000", "--kdim", "64", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    args = ["--gpus", "2", "--rows", "10000000", "--kdim", "64", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
     good = _run([sys.executable, "bench.py"] + args, LK_DIST_BACKEND="gloo", LK_FORCE_DEVICE="0")
     assert good["config"]["parity"]["ok"] is True and 3 * 64 <= good["comm"]["allreduce"]["launches"] <= 3 * 64 + 2
     # the hook variable alone (no opt-in) changes nothing
@@ -227,3 +227,42 @@ def test_a_wrong_reduction_ends_the_run_nonzero_with_its_line_printed():
     assert "config.parity.ok is false" in out.stderr
     import re
     assert len(re.findall(r"exitcode\s*: 4", out.stderr)) >= 1 or "exit 4" in out.stderr
+
+
+def test_dump_outputs_writes_the_last_factorisation_and_a_plain_line_stays_lean(tmp_path):
+    """--dump-outputs DIR: H, info and a fixed, seeded sample of the basis rows of the last timed factorisation, float64, within 64 MB;
+    the same command writes the same files, a two-rank run the same numbers to rounding, and the basis rows are the oracle's.  A plain
+    line carries no CPU baseline, context leg or parity check (those are --full's); --steps is the number of timed steps."""
+    import numpy as np
+    import bench
+    from oracle import oracle as ora
+    n, m = 200_003, 16
+    args = ["--rows", str(n), "--kdim", str(m), "--steps", "3", "--warmup", "1"]
+    d1, d1b, d2 = (str(tmp_path / k) for k in ("one", "one_again", "two"))
+    h1 = str(tmp_path / "h1.npy")
+    one = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", d1, "--dump-h", h1] + args)
+    assert one["steps"] == 3 and one["ms_per_step"] * one["value"] == pytest.approx(1e3 * m, rel=1e-9)
+    assert "cpu_baseline" not in one and "launch_bound_regime" not in one and one["config"]["parity"] is None
+    got = {f: np.load(os.path.join(d1, f)) for f in ("H.npy", "info.npy", "X_rows.npy")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in got) <= 64 << 20
+    assert np.array_equal(got["H.npy"], np.load(h1)) and got["info.npy"].tolist() == [0.0]
+    rows = np.unique(np.random.default_rng(bench.DUMP_ROWS_SEED).integers(0, n, size=min(n, 16384), dtype=np.int64))
+    assert got["X_rows.npy"].shape == (rows.size, m + 1)
+    _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", d1b] + args)
+    for f in got:
+        assert np.array_equal(np.load(os.path.join(d1b, f)), got[f]), f                   # same arguments, same inputs, same outputs
+    _run([sys.executable, "bench.py", "--gpus", "2", "--dump-outputs", d2] + args, LK_DIST_BACKEND="gloo", LK_FORCE_DEVICE="0")
+    X2 = np.load(os.path.join(d2, "X_rows.npy"))
+    assert X2.shape == got["X_rows.npy"].shape and np.abs(X2 - got["X_rows.npy"]).max() <= 1e-12 * np.abs(got["X_rows.npy"]).max()
+    # the basis rows against the oracle's factorisation of the same workload
+    Xo = np.zeros((n, m + 1), order="F")
+    Ho = np.zeros((m + 1, m), order="F")
+    ora.fill_counter(Xo[:, 0], 7)
+    Xo[:, 0] /= np.linalg.norm(Xo[:, 0])
+    assert ora.arnoldi(ora.DiagLinOp(1.0, 1.0 / n), Xo, Ho) == 0
+    Xs = Xo[rows]
+    for j in range(m + 1):
+        assert np.abs(got["X_rows.npy"][:, j] - Xs[:, j]).max() <= 1e-11 * np.abs(Xs[:, j]).max(), j
+    for j in range(m):
+        assert np.abs(got["H.npy"][:, j] - Ho[:, j]).max() <= 1e-12 * np.abs(Ho[:, j]).max(), j

@@ -9,7 +9,7 @@ D=$R/gpurun_out/$TAG
 mkdir -p "$D"; echo "$COMMIT" > "$D/commit.txt"
 python3 -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.kernel_source_hash())" > "$D/kernel_source_sha256.txt"
 cd /tmp; export TMPDIR=/tmp
-python3 "$R/bench.py" > "$D/bench_default.log" 2> "$D/bench_default.err"
+python3 "$R/bench.py" --full > "$D/bench_default.log" 2> "$D/bench_default.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$D/stats.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_fetch" -o bench -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline > "$D/pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$D/pmc_write" -o bench -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline > "$D/pmc_write.log" 2>&1
@@ -25,7 +25,7 @@ python3 "$R/tools/bench_wide.py" 1e7 f64 > "$D/wide_f64.log" 2>&1
 python3 "$R/tools/bench_wide.py" 5e6 c128 > "$D/wide_c128.log" 2>&1
 LK_LINCOMB_SCAN=1 python3 "$R/tools/bench_lincomb.py" gemm_mfma_min=100 > "$D/lincomb_scan_valu.log" 2>&1
 LK_LINCOMB_SCAN=1 python3 "$R/tools/bench_lincomb.py" gemm_mfma_min=1 > "$D/lincomb_scan_mfma.log" 2>&1
-for op in dense lap5 csr; do python3 "$R/bench.py" --operator $op --steps 3 --warmup 1 > "$D/bench_$op.log" 2> "$D/bench_$op.err"; done
+for op in dense lap5 csr; do python3 "$R/bench.py" --operator $op --steps 3 --warmup 1 --full > "$D/bench_$op.log" 2> "$D/bench_$op.err"; done
 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/dense" -o dense -- python3 "$R/bench.py" --operator dense --steps 1 --warmup 1 --no-cpu-baseline > "$D/dense_traced.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_wide_fetch" -o wide -- python3 "$R/tools/bench_wide.py" 4e6 f64 > "$D/pmc_wide_fetch.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_block_fetch" -o block -- python3 "$R/tools/bench_block_dgs.py" 32 1 > "$D/pmc_block_fetch.log" 2>&1

@@ -21,7 +21,7 @@ for P in 2 4 8; do
 done
 (cd "$R" && python3 tools/make_profiles.py "$D" onbox > "$D/make_profiles_onbox.log" 2>&1)     # profiles/pmc_traffic.json of THIS build, on the box
 # -- 2. the bench lines (now with `traffic`), the kernel trace, the shard lines, the 8-process line
-python3 "$R/bench.py" > "$D/bench_default.log" 2> "$D/bench_default.err"
+python3 "$R/bench.py" --full > "$D/bench_default.log" 2> "$D/bench_default.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$D/stats.log" 2>&1
 for P in 2 4 8; do python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --shard-of $P > "$D/shard_$P.log" 2>/dev/null; done
 (cd "$R" && LK_DIST_BACKEND=gloo LK_FORCE_DEVICE=0 GLOO_SOCKET_IFNAME=lo python3 bench.py --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline > "$D/cfg5_8rank_one_gpu.log" 2> "$D/cfg5_8rank_one_gpu.err")
@@ -49,7 +49,7 @@ python3 "$R/tools/bench_small_arnoldi.py" f64 > "$D/small_arnoldi_f64.log" 2>&1
 python3 "$R/tools/bench_small_arnoldi.py" c128 > "$D/small_arnoldi_c128.log" 2>&1
 python3 "$R/tools/resident_phases.py" f64 sizes=1000,175000,300000,1000000 ks=1,8,32,64,128 > "$D/resident_phases_f64.log" 2>&1
 python3 "$R/tools/bench_block_arnoldi.py" f64 > "$D/block_arnoldi_f64.log" 2>&1
-for op in dense lap5 csr; do python3 "$R/bench.py" --operator $op --steps 3 --warmup 1 > "$D/bench_$op.log" 2> "$D/bench_$op.err"; done
+for op in dense lap5 csr; do python3 "$R/bench.py" --operator $op --steps 3 --warmup 1 --full > "$D/bench_$op.log" 2> "$D/bench_$op.err"; done
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_block_wide_fetch" -o block -- python3 "$R/tools/bench_block_wide.py" 4e6 panels_only > "$D/pmc_block_wide_fetch.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/block_stats" -o block -- python3 "$R/tools/bench_block_dgs.py" 32 1 > "$D/block_stats.log" 2>&1
 python3 "$R/tools/profile_eigs_cycle.py" 5 > "$D/eigs_profile.log" 2>&1
