@@ -443,7 +443,8 @@ int lk_bidiag(lk_linop_t A, lk_basis_t U, lk_basis_t V, double *B, int64_t ldb, 
  * against the j columns before it with beta = R(:j-1, j) (:131-134), beta = ||q_j|| (:135), NaN aborts (:137-143); beta < tol => info = j
  * (first such column), R(j, j) = 0, the column is re-drawn from the counter generator (stream 0x5EED + panel column + 1), orthogonalised
  * again and its new norm taken (:146-162), else R(j, j) = beta; q_j scaled by 1 / beta (:164).  R: host p x p column-major (leading
- * dimension ldr elements) of the basis dtype, zeroed by the call.  Host-synchronous, column by column. */
+ * dimension ldr elements) of the basis dtype, zeroed by the call; rows p..ldr-1 are not touched (the reference's R = zero, :125, covers a
+ * larger R as well: the caller clears them).  Host-synchronous, column by column. */
 int lk_qr(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, double tol, int *info);
 /* arnoldi(A, X, H, info, kstart, kend, tol, transpose, blksize): src/Krylov/arnoldi.fypp:8-76 with blksize = p > 1 (p = 1 is lk_arnoldi).
  * X holds (kdim + 1) p columns (kdim = (ncols - p) / p, :26), H is host ((kdim + 1) p x kdim p), column-major, leading dimension ldh.

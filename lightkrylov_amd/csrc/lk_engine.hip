@@ -3599,6 +3599,14 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
     if (c->prof) prof_collect(c);
     const int stop_step = *c->stop_host;
     *done = stop_step ? stop_step : klast;
+    if (*cancelled && stop_step && resident_applies(X, stop_step)) {
+        // a look-ahead step beyond the delivered ones stopped the device: the caller reads no slot of a cancelled batch, but a single launch
+        // that gave up there left the abort word raised -- clear it here, or the next launch on this context finds it at entry
+        const double status = c->step_red_host[(size_t)(stop_step - k0) * slot_doubles + 2 * (size_t)rs + (size_t)stop_step * ED + 1];
+        if (status == 1.0) LKCHK(resident_recover(c));
+        else if (status != 0.0)
+            return fail(LK_ERR_HIP, "lk_arnoldi_segments: the single-launch Gram-Schmidt step failed after its first phase (status %g)", status);
+    }
     return LK_OK;
 }
 
@@ -3945,6 +3953,7 @@ static int arnoldi_impl(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int 
         LKCHK(arnoldi_batch_async(A, X, k, k1, tol, trans, &done, segs.empty() ? nullptr : segs.data(), (int)segs.size(), deliver, &delivered_to,
                                   &cancelled));
         if (cancelled) break;                                    // the caller asked to stop: columns beyond the last report are not delivered
+                                                                 // (a give-up among the steps run ahead has been cleared by the batch)
         LKCHK(fill(delivered_to + 1, done, &stop));
         if (redo) {                                              // (the device stop flag was raised by the launch that gave up)
             report(redo - 1);

@@ -28,6 +28,7 @@
 // All blocks must be co-resident: the grid is at most one block per CU.  A wait that outlasts its deadline (another persistent
 // kernel holding part of the chip) raises the abort word: nothing has been written to y at that point (the first wait comes before any
 // store), the host runs that step on the three-sweep schedule, clears the word and pauses the single launch for a while (lk_engine.hip).
+// A launch that finds the word raised at its entry reports a give-up as well, so a word left raised costs one redo, never a wrong step.
 #pragma once
 #include "lk_kernels.hip.h"
 
@@ -370,11 +371,6 @@ __global__ __launch_bounds__(NW * 64) void dgs_onchip(LK_RES_ARGS) {
             for (int jj = 0; jj < KC; ++jj) xk[i][jj] = v2d{0.0, 0.0};
         }
     }
-    if (threadIdx.x == 0) ctl[0] = ld_agent(res_ctr(ws, RES_ABORT)) != 0u;
-    __syncthreads();
-    if (ctl[0]) return;                                   // a block that became resident after the launch was given up
-    const long long start = wall_clock64();
-    const long long deadline = start + spin_ticks, deadline_late = deadline + 1000000000ll;
     double *r2 = out + 2 * (int64_t)rs;
     auto give_up = [&](double status) {
         if (threadIdx.x == 0) {
@@ -382,6 +378,17 @@ __global__ __launch_bounds__(NW * 64) void dgs_onchip(LK_RES_ARGS) {
             if (stop_out) *stop_out = guard.step;
         }
     };
+    if (threadIdx.x == 0) ctl[0] = ld_agent(res_ctr(ws, RES_ABORT)) != 0u;
+    __syncthreads();
+    // The word is raised: this launch was given up at its first wait before this block published anything, or an earlier launch left it
+    // raised.  Either way nothing has been written to y: block 0 reports the give-up (status + stop flag), so that the host redoes the
+    // step on the three sweeps and clears the word -- returning silently would leave the previous step's numbers in the slot.
+    if (ctl[0]) {
+        if (blockIdx.x == 0) give_up(1.0);
+        return;
+    }
+    const long long start = wall_clock64();
+    const long long deadline = start + spin_ticks, deadline_late = deadline + 1000000000ll;
     auto stamp = [&](int i) { if (blockIdx.x == 0 && threadIdx.x == 0) ws.tim[i] = wall_clock64(); };
     if (blockIdx.x == 0 && threadIdx.x == 0) ws.tim[0] = t_entry;   // (taken at kernel entry: the abort-word load above returns behind every tile load,
                                                                     //  a stamp here would hide the whole panel read from phase 1)
@@ -439,7 +446,8 @@ __global__ __launch_bounds__(NW * 64) void dgs_onchip(LK_RES_ARGS) {
         if (i < nb) nrm += yk[i].x * yk[i].x + yk[i].y * yk[i].y;
     block_sums_acc<CPLX, KC, NW>(acc, nrm, false, k, WC, kcw, T, Q, mine);
     stamp(5);
-    if (!grid_sum<NTHR>(ws, 2, k * ED, (k + 1) * ED, mine, h3, ctl, T, deadline_late)) { give_up(1.0); return; }   // (y not stored yet: still a clean give-up)
+    // a block whose last wait times out has stored nothing, but the blocks that saw every partial may already be storing y'': a failure
+    if (!grid_sum<NTHR>(ws, 2, k * ED, (k + 1) * ED, mine, h3, ctl, T, deadline_late)) { give_up(2.0); return; }
     stamp(6);
     const double nr = sqrt(fabs(h3[k * ED]));
     res_publish<NTHR>(h1, h2, h3[k * ED], k, ED, out, rs, tol_break, stop_out, guard.step);
@@ -508,14 +516,6 @@ __global__ __launch_bounds__(NW * 64) void dgs_resident(LK_RES_ARGS) {
     __shared__ double T[(NW * KC + NW) * RES_ROW], Q[(NW * KC + NW) * 4];
     __shared__ __attribute__((aligned(16))) double mine[CAPS], h1[CAPS], h2[CAPS], h3[CAPS];
     __shared__ int ctl[2];
-    if (threadIdx.x == 0) ctl[0] = ld_agent(res_ctr(ws, RES_ABORT)) != 0u;
-    __syncthreads();
-    if (ctl[0]) return;                                   // a block that became resident after the launch was given up
-    // the FIRST wait is the one that can starve (a block not yet resident); past it every block is on the chip.  The later waits
-    // still carry a (generous) bound so that a defect can never hang the device; one firing there is reported as a failure.
-    const long long start = wall_clock64();
-    const long long deadline = start + spin_ticks, deadline_late = deadline + 1000000000ll;
-    const ResGeom q = res_geom<CPLX, NW>(k, n, ldx, WC, kcw);
     const int nslots = (k + 1) * ED;
     double *r2 = out + 2 * (int64_t)rs;
     auto give_up = [&](double status) {
@@ -524,6 +524,17 @@ __global__ __launch_bounds__(NW * 64) void dgs_resident(LK_RES_ARGS) {
             if (stop_out) *stop_out = guard.step;
         }
     };
+    if (threadIdx.x == 0) ctl[0] = ld_agent(res_ctr(ws, RES_ABORT)) != 0u;
+    __syncthreads();
+    if (ctl[0]) {                                         // given up, or left raised: fail closed (as in dgs_onchip)
+        if (blockIdx.x == 0) give_up(1.0);
+        return;
+    }
+    // the FIRST wait is the one that can starve (a block not yet resident); past it every block is on the chip.  The later waits
+    // still carry a (generous) bound so that a defect can never hang the device; one firing there is reported as a failure.
+    const long long start = wall_clock64();
+    const long long deadline = start + spin_ticks, deadline_late = deadline + 1000000000ll;
+    const ResGeom q = res_geom<CPLX, NW>(k, n, ldx, WC, kcw);
     auto stamp = [&](int i) { if (blockIdx.x == 0 && threadIdx.x == 0) ws.tim[i] = wall_clock64(); };
     stamp(0);
     res_phase<CPLX, KC, NW, 1>(X, y, n, k, q, nullptr, nullptr, WC, kcw, false, u_lds, T, Q, mine);
@@ -537,7 +548,8 @@ __global__ __launch_bounds__(NW * 64) void dgs_resident(LK_RES_ARGS) {
     stamp(2);
     res_phase<CPLX, KC, NW, 2>(X, y, n, k, q, h1, nullptr, WC, kcw, (flags & 2) != 0, u_lds, T, Q, mine);
     stamp(3);
-    if (!grid_sum<NTHR>(ws, 1, 0, nslots, mine, h2, ctl, T, deadline_late)) { give_up(1.0); return; }
+    // the blocks that saw every partial of this sum go on to store y'' (phase 3): a wait that times out here is a failure, not a clean give-up
+    if (!grid_sum<NTHR>(ws, 1, 0, nslots, mine, h2, ctl, T, deadline_late)) { give_up(2.0); return; }
     stamp(4);
     res_phase<CPLX, KC, NW, 4>(X, y, n, k, q, h1, h2, WC, kcw, false, u_lds, T, Q, mine);
     stamp(5);

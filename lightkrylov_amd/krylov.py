@@ -131,16 +131,19 @@ def _panel_columns(Q):
 def qr(Q, R: np.ndarray, tol: float = atol_dp) -> int:
     """qr_no_pivoting: in-place DGS-based QR of the basis Q, R upper triangular.
     src/Krylov/qr.fypp:116-167.  Returns info (index of the first colinear column, 1-based)."""
+    p = len(Q)
+    if R.ndim != 2 or R.shape[0] < p or R.shape[1] < p:
+        raise ValueError(f"qr: R has shape {R.shape}, the factor of {p} columns needs at least ({p}, {p})")
+    R[...] = 0                                                                      # :125 (all of R, also beyond p x p)
     # columns of ONE device panel: the whole factorisation inside the engine (lk_qr)
     cols = _panel_columns(Q)
-    if cols is not None and R.flags.f_contiguous and R.dtype == cols[0].dtype and R.shape[0] >= len(Q):
+    if cols is not None and R.flags.f_contiguous and R.dtype == cols[0].dtype:
         B, j0, p = cols
         cinfo = C.c_int()
         _capi.check(B._lib.lk_qr(B._h, j0, p, R.ctypes.data_as(_DP), R.shape[0], float(tol), C.byref(cinfo)))
         return cinfo.value
     info, flag = 0, False
-    R[...] = 0
-    for j in range(len(Q)):
+    for j in range(p):
         qj = Q[j]
         if j > 0:
             bj = np.zeros(j, dtype=R.dtype)

@@ -85,6 +85,26 @@ def test_qr_rank_deficient_column_is_flagged():
     assert np.abs(Qm.T @ Qm - np.eye(3)).max() < 1e-13
 
 
+def test_qr_sets_the_whole_of_a_larger_R_and_refuses_a_smaller_one():
+    """qr.fypp:125 (R = zero): an R larger than p x p comes back zero outside the factor, equal to the oracle's; an R that cannot hold
+    the p columns is refused before any column is touched"""
+    n, p = 100, 3
+    cols = [seeded(n, np.float64, 10 + j) for j in range(p)]
+    Mo = np.stack(cols, axis=1).copy(order="F")
+    Ro = np.full((p + 2, p + 2), 7.0, order="F")
+    assert ora.qr_no_pivoting(Mo, Ro) == 0
+    Q = [oracle_vector(c.copy()) for c in cols]
+    R = np.full((p + 2, p + 2), 7.0, order="F")
+    assert lk.qr(Q, R) == 0
+    assert not R[p:, :].any() and not R[:, p:].any()
+    assert np.abs(R - Ro).max() <= 1e-13 * np.abs(Ro).max()
+    for shape in ((p + 2, p - 1), (p - 1, p), (p,)):
+        Q = [oracle_vector(c.copy()) for c in cols]
+        with pytest.raises(ValueError, match="R has shape"):
+            lk.qr(Q, np.zeros(shape, order="F"))
+        assert all(np.array_equal(q.data, c) for q, c in zip(Q, cols))
+
+
 def test_generic_lanczos_equals_oracle():
     n = 64
     A = 2.5 * np.eye(n) + 0.8 * (np.eye(n, k=1) + np.eye(n, k=-1))
