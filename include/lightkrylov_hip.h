@@ -125,8 +125,9 @@ int lk_set_allgather(lk_context_t ctx, lk_allgather_fn fn, void *user);
 int lk_set_partition(lk_context_t ctx, int64_t row0, int64_t n_global);
 /* Tuning keys (integers; 28 of them -- round 6 removed every key whose other setting was measured slower and never defaulted, the
  * record of those A/Bs is docs/TUNING_LOG.md).  None changes a result beyond rounding; the ones marked [bits] change no result bit.
- *   schedule      "async_arnoldi" (1: lk_arnoldi / lk_lanczos / lk_bidiag enqueue all steps behind a device-side breakdown flag, one host
- *                 synchronisation per call; 0: one round trip per step) [bits]; "lazy", "lazy_speculate" (see lk_lazy_stats) [bits];
+ *   schedule      "async_arnoldi" (1: lk_arnoldi / lk_arnoldi_block enqueue all steps behind a device-side breakdown flag, one host
+ *                 synchronisation per call; 0: one round trip per step; lk_lanczos / lk_bidiag always enqueue and do not read the key)
+ *                 [bits]; "lazy", "lazy_speculate" (see lk_lazy_stats) [bits];
  *                 "pool_slab_cols" (columns per pool slab) [bits]
  *   single launch "resident", "resident_max_mb", "resident_onchip", "resident_rev", "resident_spin_ms" (see lk_resident_stats)
  *   sweeps        "recompute_update" (1: sweep 2 keeps y' in registers, sweep 3 re-forms it: y' never goes to HBM; 0: y' stored, sweep 3

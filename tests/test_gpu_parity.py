@@ -167,7 +167,7 @@ DGS_CASES = [(1000, 1), (1001, 2), (999, 3), (4096, 15), (4097, 16), (4099, 17),
 def test_double_gram_schmidt_step_against_oracle(ctx, dtype, n, k):
     k = min(k, n)
     Q = orthonormal_basis(n, k, dtype, 3)
-    y = seeded(n, dtype, 77)
+    y = seeded(n, dtype, 7700)                                            # (a seed of no column: the basis uses 3 .. 3 + k - 1)
     B = lk.krylov_basis_gpu(n, k + 1, dtype, ctx)
     B.upload(Q, 0)
     B.upload(y.reshape(-1, 1), k)
