@@ -123,12 +123,16 @@ int lk_set_allgather(lk_context_t ctx, lk_allgather_fn fn, void *user);
 /* row block owned by this rank: global rows [row0, row0 + n_local) of n_global; only used
  * so that counter-based rand fills are identical for every partition. */
 int lk_set_partition(lk_context_t ctx, int64_t row0, int64_t n_global);
-/* Tuning keys (integers; 28 of them -- round 6 removed every key whose other setting was measured slower and never defaulted, the
+/* Tuning keys (integers; 29 of them -- round 6 removed every key whose other setting was measured slower and never defaulted, the
  * record of those A/Bs is docs/TUNING_LOG.md).  None changes a result beyond rounding; the ones marked [bits] change no result bit.
  *   schedule      "async_arnoldi" (1: lk_arnoldi / lk_arnoldi_block enqueue all steps behind a device-side breakdown flag, one host
  *                 synchronisation per call; 0: one round trip per step; lk_lanczos / lk_bidiag always enqueue and do not read the key)
  *                 [bits]; "lazy", "lazy_speculate" (see lk_lazy_stats) [bits];
  *                 "pool_slab_cols" (columns per pool slab) [bits]
+ *                 "fuse_rowop" (1 [default]: the asynchronous lk_arnoldi batch on a diagonal operator -- lk_linop_diag_create,
+ *                 lk_linop_diag_linspace -- launches no operator kernel: the three sweeps form y = D x_k from column k-1 of the panel as
+ *                 they stream it, y never exists in memory, 3k + 3 columns per step instead of 3k + 8; 0: the operator kernel writes y
+ *                 first.  Same product, same summation order) [bits]
  *   single launch "resident", "resident_max_mb", "resident_onchip", "resident_rev", "resident_spin_ms" (see lk_resident_stats)
  *   sweeps        "recompute_update" (1: sweep 2 keeps y' in registers, sweep 3 re-forms it: y' never goes to HBM; 0: y' stored, sweep 3
  *                 on the streaming update kernel -- another summation order over the columns, so y'' changes by rounding); "store_policy"

@@ -129,6 +129,8 @@ struct lk_context_s {
     // lazy batching of the PER-OBJECT path (opt-in, tuning key "lazy"): what an unchanged LightKrylov drives
     // through the type-bound procedures -- k consecutive X(i)%dot(y), then k consecutive y%axpby(a_i, X(i), 1).
     int lap5_grid_mult = 8;    // persistent blocks per CU of the stencil operator
+    int fuse_rowop = 1;        // asynchronous Arnoldi on a diagonal operator: the three sweeps form y = D x_k from column k-1 on the fly (no operator
+                               // kernel, y never in memory: 3k+3 columns per step instead of 3k+8); 0: the operator kernel writes y as before
     int dot_colwise = 1;       // sweep 1 by panel_dot_cw (one column at a time, y in registers) instead of panel_sweep<DOT>
     int grid_mult_s3 = 0;      // blocks per CU of the two-coefficient update sweep (0: grid_mult)
     int grid_mult_s2 = 1;      // blocks per CU of the update + dot sweep (0: grid_mult).  1 is never slower than 2 and +1-6 % at small n or small k
@@ -456,12 +458,14 @@ SweepCfg sweep_cfg(lk_context_t c, int k, int64_t n, int mult = 0) {
 //   MODE 4: y'' = (y - X hin) - X hin2      (UPDATE, two coefficient sets; pairs with MODE 2, store = 0)
 // out == nullptr (update-only modes): the norm of the result is not wanted -- no finish kernel, and above all NO
 // all-reduce (the lazy flush runs at rank-dependent times; a collective there could mismatch across ranks).
+// rop.kind != ROWOP_NONE (MODE 1, 2, 4 of the asynchronous Arnoldi step on a diagonal operator): y is not read but FORMED from column
+// k-1 of X by the row-local operator (lk_kernels.hip.h, RowOp); MODE 4 writes y'' to `y`, which nothing has written before.
 // G > 1 (MODE 4 only): the two-coefficient sweep with G column groups per wave and no lane split -- the partner of a sweep 2 run
 // as launch_sweep<CPLX, 2, KC / G, NW, G>: same WC and kcw (taken from THAT configuration), so y' is re-formed bit for bit, on
 // tiles G times as tall (panel_sweep's G).
 template <bool CPLX, int MODE, int KC = (CPLX ? 8 : 16), int NW = (CPLX ? 16 : 8), int SC = 1, int G = 1>
 int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y, int64_t n, const double *hin,
-                 const double *hin2, int store, double *out) {
+                 const double *hin2, int store, double *out, const RowOp &rop) {
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
     constexpr bool UPDATE = MODE != 1, DOT = MODE <= 2;
     static_assert(KC * NW * SC >= KMAX_FUSED && KC * NW * SC <= KMAX_WIDE, "fused capacity");
@@ -477,8 +481,12 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
         if (g < 1) g = 1;
         s.grid = (int)g;
     }
-    // ALGORITHMIC bytes of the three-sweep schedule: k+1 | k+2 | k+2 columns
-    const double bytes = (double)n * ED * 8.0 * (k + 1 + (UPDATE ? 1 : 0));
+    // ALGORITHMIC bytes of the three-sweep schedule: k+1 | k+2 | k+2 columns.  With a fused row operator y is neither
+    // read nor (sweeps 1, 2) written: k | k | k+1 columns, plus the column of d an explicit diagonal reads
+    const double bytes = rop.kind != ROWOP_NONE ? (double)n * ED * 8.0 * (k + (MODE == 4 ? 1 : 0) + (rop.kind == ROWOP_DIAG ? 1 : 0))
+                                                : (double)n * ED * 8.0 * (k + 1 + (UPDATE ? 1 : 0));
+    if (rop.kind != ROWOP_NONE && (MODE == 3 || (MODE == 4 && c->stream_two && G == 1) || !rowop_fusable<CPLX, KC>))
+        return fail(LK_ERR_INVALID, "internal: this sweep takes no row operator");
     int nblocks = s.grid;
     if (MODE == 1 && c->dot_colwise) {
         // sweep 1 one column at a time (panel_dot_cw): y in registers, U KiB of contiguous rows per wave and column
@@ -500,10 +508,10 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             ProfScope ps(c, "dgs_sweep1", bytes, c->prof_ext);
             if (ps.on && ps.ext)
                 hipExtLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, ps.rec.e0, ps.rec.e1, 0, X, ldx, k,
-                                      y, n, c->partial, (int64_t)MAX_GRID, c->guard());
+                                      y, n, c->partial, (int64_t)MAX_GRID, c->guard(), rop);
             else
                 hipLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, X, ldx, k, y, n, c->partial,
-                                   (int64_t)MAX_GRID, c->guard());
+                                   (int64_t)MAX_GRID, c->guard(), rop);
         };
         // long panels: 8 loads per lane and column on 2 blocks per CU (+1-2 % over 4 on 3 at n = 10^8); short ones keep the
         // smaller tile so every CU still gets several tiles
@@ -531,10 +539,10 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             if (ps.on && ps.ext)
                 hipExtLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream,
                                       ps.rec.e0, ps.rec.e1, 0, X, ldx, k, y, n, hin, hin2, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, st,
-                                      c->guard());
+                                      c->guard(), rop);
             else
                 hipLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream, X,
-                                   ldx, k, y, n, hin, hin2, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, st, c->guard());
+                                   ldx, k, y, n, hin, hin2, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, st, c->guard(), rop);
         }
     }
     HIPCHK(hipGetLastError());
@@ -549,7 +557,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
 }
 
 template <int MODE>
-int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const double *hin2, int store, double *out) {
+int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const double *hin2, int store, double *out, const RowOp &rop = RowOp{}) {
     lk_context_t c = Bx->ctx;
     const double *X = Bx->col(c0);
     if (k > KMAX_FUSED) {
@@ -567,40 +575,40 @@ int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const dou
         // BOTH column groups of a wave-column in one wave's registers instead (panel_sweep's G = 2): same WC, kcw and summation
         // order, so y' is re-formed bit for bit, on tiles twice as tall with twice the loads in flight per lane.
         if (Bx->dtype == LK_C128) {
-            if (regs && k <= 192) return launch_sweep<true, MODE, 24, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+            if (regs && k <= 192) return launch_sweep<true, MODE, 24, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
             if (regs && c->wide_regs >= 2 && k > 2 * KMAX_FUSED && k <= 384) {
                 if constexpr (MODE == 4)
-                    if (c->wide_s3) return launch_sweep<true, 4, 48, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
-                return launch_sweep<true, MODE, 24, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+                    if (c->wide_s3) return launch_sweep<true, 4, 48, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
+                return launch_sweep<true, MODE, 24, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
             }
             if (k <= 2 * KMAX_FUSED) {
                 if constexpr (MODE == 4)
-                    if (c->wide_s3) return launch_sweep<true, 4, 32, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
-                return launch_sweep<true, MODE, 16, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+                    if (c->wide_s3) return launch_sweep<true, 4, 32, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
+                return launch_sweep<true, MODE, 16, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
             }
-            return launch_sweep<true, MODE, 16, 8, 4>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+            return launch_sweep<true, MODE, 16, 8, 4>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
         }
         if (k <= 2 * KMAX_FUSED) {
             if constexpr (MODE != 1)       // (never instantiated for the dot-only sweep: its 32-column register tile spills)
-                if (regs) return launch_sweep<false, MODE, 32, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+                if (regs) return launch_sweep<false, MODE, 32, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
             if constexpr (MODE == 4)
-                if (c->wide_s3) return launch_sweep<false, 4, 32, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
-            return launch_sweep<false, MODE, 16, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+                if (c->wide_s3) return launch_sweep<false, 4, 32, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
+            return launch_sweep<false, MODE, 16, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
         }
         if (regs && c->wide_regs >= 2 && k <= 384) {
             if constexpr (MODE == 4)
-                if (c->wide_s3) return launch_sweep<false, 4, 48, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
-            return launch_sweep<false, MODE, 24, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+                if (c->wide_s3) return launch_sweep<false, 4, 48, 8, 1, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
+            return launch_sweep<false, MODE, 24, 8, 2>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
         }
-        return launch_sweep<false, MODE, 16, 8, 4>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+        return launch_sweep<false, MODE, 16, 8, 4>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
     }
     if (Bx->dtype == LK_C128) {
         // complex block shape: 16 waves x 8 columns for narrow bases, 8 waves x 16 columns beyond 32 columns (half the
         // waves per barrier and per LDS exchange: +1-9 % per sweep at k >= 64, A/B in DESIGN.md; "cplx_wide" = threshold, 0 disables).
         // The choice depends on k only, so the three sweeps of one DGS always share it (sweep 3 re-forms y' in sweep 2's order).
         // (the dot-only sweep is free to choose on its own and prefers the narrow shape up to ~56 columns)
-        if (c->cplx_wide && k > (MODE == 1 ? c->cplx_wide + 24 : c->cplx_wide)) return launch_sweep<true, MODE, 16, 8>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
-        return launch_sweep<true, MODE>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+        if (c->cplx_wide && k > (MODE == 1 ? c->cplx_wide + 24 : c->cplx_wide)) return launch_sweep<true, MODE, 16, 8>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
+        return launch_sweep<true, MODE>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
     }
     // "kc32" (round 4): the real kind's update sweeps on 32-column register tiles (the 129..256-column shape) for narrow bases too:
     // k > kc32 columns run 8 waves x 32 columns (WC = 2 / 4 wave-columns, tiles 2-4 times as tall) -- sweeps 2 and 3 together, they
@@ -615,9 +623,9 @@ int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const dou
         const int64_t nref = c->n_global > 0 ? c->n_global : Bx->n;
         const int kc32 = c->kc32 >= 0 ? c->kc32 : (nref >= ((int64_t)1 << 25) ? 32 : 0);
         if constexpr (MODE == 2 || MODE == 4)
-            if (kc32 && k > kc32) return launch_sweep<false, MODE, 32, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+            if (kc32 && k > kc32) return launch_sweep<false, MODE, 32, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
     }
-    return launch_sweep<false, MODE>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out);
+    return launch_sweep<false, MODE>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
 }
 
 // M(:, q) = X(:, c0:c0+k)^H Y(:, jy0+q), q < pn <= 4 (k <= KMAX_FUSED), in ONE pass over X; results land in c->red as
@@ -1359,16 +1367,18 @@ int fused_sub_with_dots(lk_context_t c) {
 
 // Core of double_gram_schmidt_step for one vector; results stay in c->red (device):
 //   section 0: h1[0..k), nrm2(y)    section 1: h2[0..k), nrm2(y')   section 2 (slot k): nrm2(y'')
-int dgs_device(lk_basis_t Bx, int k, double *y, bool two_pass, double *red_base = nullptr, int stride = 0, int c0 = 0) {
+// rop (two passes with recompute_update only): y = D X(:, c0 + k - 1) is formed inside the sweeps, `y` receives y''.
+int dgs_device(lk_basis_t Bx, int k, double *y, bool two_pass, double *red_base = nullptr, int stride = 0, int c0 = 0, const RowOp &rop = RowOp{}) {
     lk_context_t c = Bx->ctx;
     double *base = red_base ? red_base : c->red;
     if (!stride) stride = red_stride(k);
     double *r0 = base, *r1 = base + stride, *r2 = base + 2 * stride;
     if (k <= KMAX_WIDE) {
-        LKCHK((sweepm<1>(Bx, c0, k, y, nullptr, nullptr, 1, r0)));    // h1 = X^H y ; ||y||^2
+        if (rop.kind != ROWOP_NONE && !(two_pass && c->recompute_update)) return fail(LK_ERR_INVALID, "internal: fused row operator needs the recomputing schedule");
+        LKCHK((sweepm<1>(Bx, c0, k, y, nullptr, nullptr, 1, r0, rop)));    // h1 = X^H y ; ||y||^2
         if (two_pass && c->recompute_update) {
-            LKCHK((sweepm<2>(Bx, c0, k, y, r0, nullptr, 0, r1)));     // y' = y - X h1 (registers only); h2 = X^H y'; ||y'||^2
-            LKCHK((sweepm<4>(Bx, c0, k, y, r0, r1, 1, r2)));          // y'' = (y - X h1) - X h2 ; ||y''||^2
+            LKCHK((sweepm<2>(Bx, c0, k, y, r0, nullptr, 0, r1, rop)));     // y' = y - X h1 (registers only); h2 = X^H y'; ||y'||^2
+            LKCHK((sweepm<4>(Bx, c0, k, y, r0, r1, 1, r2, rop)));          // y'' = (y - X h1) - X h2 ; ||y''||^2
         } else if (two_pass) {
             LKCHK((sweepm<2>(Bx, c0, k, y, r0, nullptr, 1, r1)));     // y' = y - X h1 ; h2 = X^H y' ; ||y'||^2
             LKCHK((sweepm<3>(Bx, c0, k, y, r1, nullptr, 1, r2)));     // y'' = y' - X h2 ; ||y''||^2
@@ -1675,6 +1685,7 @@ int lk_set_tuning(lk_context_t c, const char *key, int value) {
         return LK_OK;
     }
     if (!strcmp(key, "dot_colwise")) { c->dot_colwise = value != 0; return LK_OK; }
+    if (!strcmp(key, "fuse_rowop")) { c->fuse_rowop = value != 0; return LK_OK; }
     if (!strcmp(key, "cw_u")) { c->cw_u = value == 8 ? 8 : (value == 4 ? 4 : 0); return LK_OK; }
     if (!strcmp(key, "cw_grid_mult")) { if (value < 1 || value > 16) return fail(LK_ERR_INVALID, "lk_set_tuning: cw_grid_mult must be in [1, 16]"); c->cw_grid_mult = value; return LK_OK; }
     if (!strcmp(key, "xhy_db")) { c->xhy_db = value < 0 ? 0 : (value > 2 ? 2 : value); return LK_OK; }
@@ -3504,6 +3515,22 @@ static int ensure_step_buffers(lk_context_t c, int nsteps, int stride) {
 // LK_OK, an error, or LK_STOP_REQUESTED (the caller's progress function asked to stop): nothing more is enqueued then -- at most
 // SEG_LOOKAHEAD steps beyond the delivered ones have run -- and *cancelled is set.  A device-side stop inside a segment ends the
 // deliveries there; the caller processes the stopped step after the final synchronisation, exactly as in the unsegmented case.
+// The row-local form of A for the sweeps of an asynchronous step (RowOp), or kind ROWOP_NONE: A is not diagonal, "fuse_rowop" is 0, or
+// the schedule is not the recomputing three-sweep one (the only one whose sweeps all start from the ORIGINAL y).
+// Complex bases beyond KMAX_FUSED columns keep the operator kernel: their register tiles have no room (rowop_fusable).
+static RowOp fused_rowop(lk_linop_t A, lk_basis_t X, int k, int trans) {
+    lk_context_t c = X->ctx;
+    RowOp r{};
+    if (!c->fuse_rowop || !c->recompute_update || c->stream_two || A->dtype != X->dtype || A->n != X->n) return r;
+    if (X->dtype == LK_C128 && k > KMAX_FUSED) return r;
+    if (A->kind == OP_DIAG_LIN && X->dtype == LK_F64) {
+        r.kind = ROWOP_LIN; r.d0 = A->d0; r.dstep = A->dstep; r.row0 = A->row0;
+    } else if (A->kind == OP_DIAG) {
+        r.kind = ROWOP_DIAG; r.d = A->dev; r.conj = trans && X->dtype == LK_C128;
+    }
+    return r;
+}
+
 constexpr int SEG_LOOKAHEAD = 24;
 constexpr int LK_STOP_REQUESTED = 1;
 static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, double tol, int trans, int *done, const int *seg_last, int nseg,
@@ -3537,21 +3564,25 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
             const int k = enq;
             c->guard_step = k;
             double *slot = c->step_red + (size_t)(k - k0) * slot_doubles;
-            rc = lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, k - 1, X, k);
+            const bool single = resident_applies(X, k);
+            // diagonal operator on the three-sweep schedule: no operator kernel, the sweeps form y = D x_k from column k-1 themselves and
+            // sweep 3 writes y'' into column k (y never exists in memory).  The single launch still takes a materialised y.
+            const RowOp rop = single ? RowOp{} : fused_rowop(A, X, k, trans);
+            if (rop.kind == ROWOP_NONE) rc = lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, k - 1, X, k);
+            else X->touch(k);
             if (rc != LK_OK) break;
             c->span_first = nullptr;
-            const bool single = resident_applies(X, k);
             // cache-resident panel: both passes, the normalise and the breakdown test in ONE launch (lk_resident.hip.h)
             if (single) rc = dgs_resident_launch(X, k, X->col(k), slot, rs, true, ATOL_DP, tol_break, c->stop_dev);
             else {
                 resident_note_fallback(X, k);
-                rc = dgs_device(X, k, X->col(k), true, slot, rs);
+                rc = dgs_device(X, k, X->col(k), true, slot, rs, 0, rop);
             }
             if (rc != LK_OK) break;
             if (c->prof && c->span_first) {          // "dgs" = first sweep's start .. the end of the last reduction, no events of its own
                 ProfRec span;
                 span.e0 = c->span_first; span.e1 = c->span_last; span.tag = "dgs"; span.borrowed = true;
-                span.bytes = (double)X->n * ED * 8.0 * (3.0 * k + 5.0);
+                span.bytes = (double)X->n * ED * 8.0 * (rop.kind == ROWOP_NONE ? 3.0 * k + 5.0 : 3.0 * k + 1.0 + (rop.kind == ROWOP_DIAG ? 3.0 : 0.0));
                 c->prof_pending.push_back(span);
             }
             if (!single) rc = scal_launch(X, k, 1.0, 0.0, slot + 2 * rs + (size_t)k * ED, ATOL_DP, c->stop_dev, tol_break);

@@ -34,6 +34,20 @@ __device__ __forceinline__ v2d cmulconj(v2d a, v2d b) {  // conj(a) * b
     return v2d{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x};
 }
 
+// The complex products of the diagonal operator with their roundings SPELLED OUT (two products, two fused multiply-adds: the form
+// the compiler contracts cmul / cmulconj to in k_diag), so that k_diag and the sweeps that form y = D x on the fly (rowop_y) round
+// alike whatever surrounds the call.
+__device__ __forceinline__ v2d diag_cmul(v2d a, v2d b) {
+#pragma clang fp contract(off)
+    const double t1 = a.y * b.y, t2 = a.y * b.x;
+    return v2d{fma(a.x, b.x, -t1), fma(a.x, b.y, t2)};
+}
+__device__ __forceinline__ v2d diag_cmulconj(v2d a, v2d b) {  // conj(a) * b
+#pragma clang fp contract(off)
+    const double t1 = a.y * b.y, t2 = a.y * b.x;
+    return v2d{fma(a.x, b.x, t1), fma(a.x, b.y, -t2)};
+}
+
 // Sum over the 64 lanes of a wave, result in EVERY lane.  Data-parallel-primitive moves inside the 16-lane rows
 // (quad_perm x2, row_half_mirror, row_mirror: VALU cross-lane operands, no LDS crossbar) and four v_readlane for the rows:
 // ~30 instructions, against ~1200 cycles for the six dependent ds_bpermute pairs of a __shfl_down tree -- which made the
@@ -136,6 +150,61 @@ __device__ __forceinline__ v2d load_y(const double *__restrict__ y, int64_t r, i
     }
 }
 
+// Row-local operator fused into a sweep (the asynchronous Arnoldi batch on a diagonal operator): y = D x_k is a function of row i
+// alone and x_k is column k-1 of the panel the sweep streams anyway, so the sweep FORMS y from that column where it would load it
+// and y never exists in memory -- no operator kernel, no y read in any of the three sweeps, sweep 3 writes y'' into column k.
+// A runtime argument (block-uniform branch), not a template parameter: every kernel keeps its one instance per shape.
+//   ROWOP_NONE: y is loaded (every other caller)
+//   ROWOP_LIN : d_i = fma(dstep, (double)(row0 + i), d0), real kind only  (k_diag_linspace)
+//   ROWOP_DIAG: d_i = d[i];  complex: d_i x_i, or conj(d_i) x_i with `conj` (k_diag)
+struct RowOp {
+    int kind;
+    int conj;
+    double d0, dstep;
+    int64_t row0;
+    const double *d;
+};
+enum { ROWOP_NONE = 0, ROWOP_LIN = 1, ROWOP_DIAG = 2 };
+
+// The product exactly as the operator kernel rounds it, and ROUNDED before the caller's `yv -= u` or dot FMAs see it: contraction
+// is off inside (the complex products are written out with the fused multiply-adds k_diag compiles to), and the result passes
+// through an empty asm so that no later pass can fold the multiplication into its consumer.
+template <bool CPLX>
+__device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict__ x, int64_t r, int64_t n, bool full) {
+#pragma clang fp contract(off)
+    auto ld = [&](const double *__restrict__ p) -> v2d { return load_y<CPLX>(p, r, n, full); };
+    const v2d b = ld(x);
+    v2d yv;
+    if constexpr (CPLX) {
+        const v2d a = ld(op.d);
+        yv = op.conj ? diag_cmulconj(a, b) : diag_cmul(a, b);
+    } else if (op.kind == ROWOP_LIN) {
+        const double g = (double)(op.row0 + r);
+        yv = v2d{fma(op.dstep, g, op.d0), fma(op.dstep, g + 1.0, op.d0)} * b;
+        if (!full) {                                   // rows beyond n are zeros whatever d_i would be there
+            if (r >= n) yv.x = 0.0;
+            if (r + 1 >= n) yv.y = 0.0;
+        }
+    } else {
+        yv = ld(op.d) * b;
+    }
+    asm("" : "+v"(yv.x));
+    asm("" : "+v"(yv.y));
+    return yv;
+}
+// y of a sweep: loaded, or formed from column k-1 (`xk`) of the panel.  FUSABLE = false compiles the operator out of an instance
+// whose register tile has no room for the second stream (the launcher never hands such an instance an operator).
+template <bool CPLX, bool FUSABLE = true>
+__device__ __forceinline__ v2d load_y_op(const RowOp &op, const double *__restrict__ y, const double *__restrict__ xk, int64_t r,
+                                         int64_t n, bool full) {
+    if constexpr (FUSABLE)
+        if (op.kind != ROWOP_NONE) return rowop_y<CPLX>(op, xk, r, n, full);
+    return load_y<CPLX>(y, r, n, full);
+}
+// complex register tiles of more than 16 columns (bases of 129..384 complex columns) are full: the explicit diagonal's second stream
+// spilled there, so those instances keep loading a materialised y
+template <bool CPLX, int KC> constexpr bool rowop_fusable = !(CPLX && KC > 16);
+
 // UNIFORM = false: nc differs between the lanes of a wave (lane-split sweeps): one predicated load per column, no
 // wave-uniform fast path.
 template <bool CPLX, int KC, bool UNIFORM = true>
@@ -188,10 +257,11 @@ __device__ __forceinline__ void load_cols_sbase(const double *__restrict__ Xt, i
     }
 }
 
-template <bool CPLX, int KC, bool UNIFORM = true>
+template <bool CPLX, int KC, bool UNIFORM = true, bool FUSABLE = true>
 __device__ __forceinline__ void load_tile(const double *__restrict__ Xw, int64_t colstride, const double *__restrict__ y,
-                                          int64_t r, int64_t n, bool full, int nc, v2d (&xv)[KC], v2d &yv) {
-    yv = load_y<CPLX>(y, r, n, full);
+                                          int64_t r, int64_t n, bool full, int nc, v2d (&xv)[KC], v2d &yv, const RowOp &rop,
+                                          const double *__restrict__ xk) {
+    yv = load_y_op<CPLX, FUSABLE>(rop, y, xk, r, n, full);
     load_cols<CPLX, KC, UNIFORM>(Xw, colstride, r, n, full, nc, xv);
 }
 
@@ -236,13 +306,15 @@ __device__ __forceinline__ void store_rows(double *__restrict__ y, int64_t r, in
 // groups' shares are then added exactly as `across_groups` adds them, so y' = y - X h1 comes out BIT FOR BIT as sweep 2 formed it
 // (the condition for dropping the y' store), while the tile is G times as tall and every lane has G times as many loads in
 // flight: the update-only sweep has no accumulators to keep, so the registers the lane split spends on them hold columns instead.
+// (second launch bound: the narrow complex two-coefficient sweep sits at 62 of the 64 registers that let two of its 1024-thread blocks
+// share a CU -- 8 waves per SIMD; the operator's second stream must not push it over)
 template <bool CPLX, int KC, int NW, bool UPDATE, bool DOT, bool TWO, int SC = 1, int G = 1>
-__global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict__ X, int64_t ldx, int k,
+__global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 : 1) void panel_sweep(const double *__restrict__ X, int64_t ldx, int k,
                                                         double *__restrict__ y, int64_t n,
                                                         const double *__restrict__ hin,
                                                         const double *__restrict__ hin2,
                                                         double *__restrict__ partial, int64_t pstride,
-                                                        int WC, int kcw, int store, Guard guard) {
+                                                        int WC, int kcw, int store, Guard guard, RowOp rop) {
     static_assert(!TWO || (UPDATE && !DOT), "TWO is the update-only sweep with two coefficient sets");
     static_assert(SC == 1 || SC == 2 || SC == 4, "lane split");
     static_assert(G == 1 || G == 2 || G == 4, "column groups per wave");
@@ -254,6 +326,7 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict_
     constexpr int WROWS = LG * ROWS;     // rows one wave covers per tile
     constexpr int NU = TWO ? 2 : 1;
     constexpr bool BIG = KC > 16;        // wide register tile: scalar-base addressing (SC = 1), slim accumulators
+    constexpr bool FUSE = rowop_fusable<CPLX, KC>;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -337,6 +410,7 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict_
     const double *Xw = X + (int64_t)c0 * ldx * ED;
     const int64_t colstride = ldx * ED;  // doubles between consecutive columns
     const int64_t roff = (int64_t)wr * WROWS + (int64_t)rl * ROWS;
+    const double *xk = X + (int64_t)(k - 1) * colstride;     // rop: y is formed from column k-1 (x_k) instead of being loaded
     int buf = 0;
 
     // tile order.  Default: cyclic over the whole grid (block b takes tiles b, b + G, ...).  Bit 4 of `store` (A/B knob
@@ -354,7 +428,7 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict_
         v2d yv;
         if constexpr (G > 1) {
             // slot g * KCG + j <- column c0 + g * kcw + j (j < kcw, column < k); the other slots hold zeros
-            yv = load_y<CPLX>(y, r, n, full);
+            yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, full);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 int ng = nc - g * kcw;
@@ -374,13 +448,13 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict_
             }
         } else if constexpr (BIG && SC == 1) {
             if (full) {
-                yv = load_y<CPLX>(y, r, n, true);
+                yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, true);
                 load_cols_sbase<KC>(Xw + (t * tile_rows + (int64_t)wr * WROWS) * ED, colstride, (uint32_t)(rl * ROWS * ED * 8), nc, xv);
             } else {
-                load_tile<CPLX, KC, false>(Xw, colstride, y, r, n, false, nc, xv, yv);
+                load_tile<CPLX, KC, false, FUSE>(Xw, colstride, y, r, n, false, nc, xv, yv, rop, xk);
             }
         } else {
-            load_tile<CPLX, KC, SC == 1>(Xw, colstride, y, r, n, full, nc, xv, yv);
+            load_tile<CPLX, KC, SC == 1, FUSE>(Xw, colstride, y, r, n, full, nc, xv, yv, rop, xk);
         }
 
         if constexpr (UPDATE) {
@@ -546,7 +620,7 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep(const double *__restrict_
 template <bool CPLX, int U>
 __global__ __launch_bounds__(256) void panel_dot_cw(const double *__restrict__ X, int64_t ldx, int k,
                                                     const double *__restrict__ y, int64_t n, double *__restrict__ partial,
-                                                    int64_t pstride, Guard guard) {
+                                                    int64_t pstride, Guard guard, RowOp rop) {
     if (stopped(guard)) return;
     constexpr int ROWS = K<CPLX>::ROWS;
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
@@ -560,6 +634,7 @@ __global__ __launch_bounds__(256) void panel_dot_cw(const double *__restrict__ X
     const int64_t tile_rows = (int64_t)SEG * U;
     const int64_t ntiles = (n + tile_rows - 1) / tile_rows;
     const int64_t colstride = ldx * ED;
+    const double *xk = X + (int64_t)(k - 1) * colstride;     // rop: y is formed from column k-1 (x_k) instead of being loaded
     double nrm = 0.0;
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int64_t r0 = t * tile_rows + (int64_t)threadIdx.x * ROWS;
@@ -567,7 +642,7 @@ __global__ __launch_bounds__(256) void panel_dot_cw(const double *__restrict__ X
         v2d yv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            yv[u] = load_y<CPLX>(y, r0 + (int64_t)u * SEG, n, full);
+            yv[u] = load_y_op<CPLX>(rop, y, xk, r0 + (int64_t)u * SEG, n, full);
             nrm += yv[u].x * yv[u].x + yv[u].y * yv[u].y;
         }
         for (int j = 0; j < k; ++j) {
@@ -3102,7 +3177,7 @@ __global__ __launch_bounds__(256) void k_diag(const double *__restrict__ d, cons
     v2d *yv = reinterpret_cast<v2d *>(y);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
         v2d a = dv[i], b = xv[i];
-        if constexpr (CPLX) yv[i] = conj_d ? cmulconj(a, b) : cmul(a, b);
+        if constexpr (CPLX) yv[i] = conj_d ? diag_cmulconj(a, b) : diag_cmul(a, b);
         else yv[i] = a * b;
     }
     if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) y[nd - 1] = d[nd - 1] * x[nd - 1];

@@ -87,8 +87,10 @@ def traffic_record(sub_fetch, sub_write, shard_of):
         calib = (8.0 * n_local) / (kb / cnt * 1024.0)
     fetch_b = sum(fetch[k][1] for k in sweeps) * 1024.0 * 2.0 / max(launches, 1)
     write_b = sum(write[k][1] for k in write if is_sweep(k)) * 1024.0 / max(launches, 1)
-    alg = 8.0 * n_local * sum(3 * k + 5 for k in range(1, m + 1)) / (3.0 * m)
-    must = 8.0 * n_local * sum(3 * k + 4 for k in range(1, m + 1)) / (3.0 * m)
+    # the diagonal operator is applied inside the sweeps ("fuse_rowop"): k | k | k + 1 columns per step, y is never
+    # read and only y'' is written -- algorithmic bytes and what the schedule must move are the same 3k + 1 columns
+    alg = 8.0 * n_local * sum(3 * k + 1 for k in range(1, m + 1)) / (3.0 * m)
+    must = alg
     flags = " --steps 1 --warmup 0 --no-cpu-baseline" + (f" --shard-of {shard_of}" if shard_of > 1 else "")
     name = f"{tag}_pmc_n{n_local:.3g}_m{m}.json".replace("+0", "").replace("+", "")
     pm = {
