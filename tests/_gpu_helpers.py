@@ -7,8 +7,52 @@ import numpy as np
 import lightkrylov_amd as lk
 from lightkrylov_amd import _capi
 from oracle import oracle as ora
+from tests._tol import _report
 
 KINDS = [np.float64, np.complex128]
+U = 2.0 ** -53
+
+
+# ---- entrywise a-priori bounds (tests/test_gpu_kernel_instances.py states them; tests/test_gpu_operator_kernels.py uses them too) --------
+def gamma(m):
+    """gamma_m of the double sum plus that of the longdouble reference (u = 2^-64), which is not exact either: a row of one product
+    rounds by up to u of it, so the measured ratio can come within 2 % of 1"""
+    m = np.asarray(m, dtype=np.float64)
+    return m * U / (1.0 - m * U) + m * 2.0 ** -64 / (1.0 - m * 2.0 ** -64)
+
+
+def is_cplx(dtype):
+    return np.dtype(dtype).kind == "c"
+
+
+def ext(A):
+    A = np.asarray(A)
+    return A.astype(np.clongdouble) if np.iscomplexobj(A) else A.astype(np.longdouble)
+
+
+def product_scale(A, B):
+    """|A| |B| (real) or (|Ar|+|Ai|)(|Br|+|Bi|) (complex): the scale of the bound; A, B already in the orientation of the product"""
+    if np.iscomplexobj(A) or np.iscomplexobj(B):
+        return (np.abs(A.real) + np.abs(A.imag)) @ (np.abs(B.real) + np.abs(B.imag))
+    return np.abs(A) @ np.abs(B)
+
+
+def check_entrywise(got, ref, scale, m, cplx, label):
+    """entrywise |got - ref| against the bound for sums of m terms (m: scalar or array broadcast like got); returns the worst ratio"""
+    got = np.asarray(got)
+    bound = (2.0 * gamma(2 * np.asarray(m) + 5) if cplx else gamma(m)) * scale
+    d = got.astype(ref.dtype) - ref
+    errs = [np.abs(d.real), np.abs(d.imag)] if cplx else [np.abs(d)]
+    ratio = 0.0
+    for e in errs:
+        e = e.astype(np.float64)
+        over = ~(e <= bound)                                        # a NaN (an entry nobody wrote) is over any bound
+        assert not over.any(), f"{label}: entry {np.argwhere(over)[0].tolist()} off by {e[over][0]:.3e} > bound {bound[over][0]:.3e}"
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(bound > 0, e / np.where(bound > 0, bound, 1.0), 0.0)
+        ratio = max(ratio, float(r.max()) if r.size else 0.0)
+    _report(label, ratio, 1.0, "entrywise gamma bound")
+    return ratio
 
 
 def seeded(n, dtype, seed):
@@ -134,3 +178,75 @@ def _arnoldi_h(ctx, n=400_003, m=12):
     X[0].rand(True, seed=7)
     assert lk.arnoldi(A, X, H) == 0
     return H, X.download()
+
+
+# ---- caller-owned panels (lk_basis_wrap) inside a larger buffer whose other rows are live -----------------------------------------
+POISON = 0x7FF8DEADBEEF0001                       # a quiet NaN whose payload no arithmetic produces
+
+
+def fit(n, dtype, layout):
+    """n as the layout can take it: ld = n must be even for the real kind; the complex kind's unpadded case is the odd one"""
+    if layout == "unpadded" and (n % 2 == 1) != (np.dtype(dtype).kind == "c"):
+        return n + 1
+    return n
+
+
+class CallerPanel:
+    """An n x ncols panel wrapped (lk_basis_wrap) inside one flat engine-owned buffer laid out as `layout` says.  `set` writes panel
+    contents, `get` reads them back and asserts that nothing outside the panel's rows changed.  The layouts (tests/test_gpu_caller_memory.py):
+    "nan_pad" / "big_pad" ld = n + 3 or n + 4 with NaN / +-1e300 padding, "offNNN" the same ld NNN bytes into a buffer of live non-zero
+    rows, "unpadded" ld = n; `extra_ld` (even) more padding rows per column, for two panels of one shape with different ld."""
+
+    def __init__(self, ctx, dtype, n, ncols, layout, seed=0, extra_ld=0):
+        dt = np.dtype(dtype)
+        cplx = dt.kind == "c"
+        es = dt.itemsize
+        if layout == "unpadded":
+            assert (n % 2 == 1) == cplx, "fit() the size first"
+            ld, head = n, 16 // es
+        else:
+            ld = n + (3 if cplx else 3 + (n + 3) % 2) + extra_ld
+            head = int(layout[3:]) // es if layout.startswith("off") else 0
+        total = head + ld * ncols + 64
+        img = np.empty(total, dtype=dt)
+        if layout in ("nan_pad", "unpadded"):
+            img.view(np.uint64)[:] = POISON
+        elif layout == "big_pad":
+            img.view(np.float64)[:] = 1e300
+            img.view(np.float64)[1::2] = -1e300
+        else:
+            ora.fill_counter(img, 9000 + seed)
+            img += np.where(img.real >= 0, 0.5, -0.5)              # |live entry| >= 0.5
+        self.inside = np.zeros(total, dtype=bool)
+        for j in range(ncols):
+            self.inside[head + j * ld:head + j * ld + n] = True
+        self.n, self.ncols, self.ld, self.head, self.dtype, self.layout = n, ncols, ld, head, dt, layout
+        self.img = img
+        self.backing = lk.krylov_basis_gpu(total, 1, dt, ctx)
+        self.backing.upload(img.reshape(-1, 1))
+        ptr = self.backing.info()[4] + head * es
+        assert ptr % 16 == 0 and (layout == "nan_pad" or layout == "big_pad" or ptr % 256 != 0)
+        h = C.c_void_p()
+        _capi.check(self.backing._lib.lk_basis_wrap(ctx._h, _capi.LK_C128 if cplx else _capi.LK_F64, n, ncols, ld, C.c_void_p(ptr),
+                                                    C.byref(h)))
+        self.B = lk.krylov_basis_gpu(n, ncols, dt, ctx, _handle=h, _owner=self.backing)
+
+    def _cols(self, buf):
+        return np.stack([buf[self.head + j * self.ld:self.head + j * self.ld + self.n] for j in range(self.ncols)], axis=1)
+
+    def set(self, A, col0=0):
+        A = np.asarray(A, dtype=self.dtype).reshape(self.n, -1, order="F")
+        buf = self.backing.download()[:, 0]
+        for j in range(A.shape[1]):
+            o = self.head + (col0 + j) * self.ld
+            buf[o:o + self.n] = A[:, j]
+        self.backing.upload(buf.reshape(-1, 1))
+
+    def get(self, what=""):
+        buf = self.backing.download()[:, 0]
+        out = ~self.inside
+        got, want = buf[out].view(np.uint64), self.img[out].view(np.uint64)
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, (f"{what} [{self.layout}, n = {self.n}, ld = {self.ld}]: {bad.size} words outside the panel changed, first at "
+                               f"outside word {int(bad[0])}: {got[bad[0]]:#x} (was {want[bad[0]]:#x})")
+        return np.asfortranarray(self._cols(buf))

@@ -18,79 +18,12 @@ import pytest
 import lightkrylov_amd as lk
 from lightkrylov_amd import _capi
 from oracle import oracle as ora
-from tests._gpu_helpers import KINDS, basis, orthonormal_basis, seeded
+from tests._gpu_helpers import KINDS, POISON, CallerPanel, basis, fit, orthonormal_basis, seeded
 from tests._tol import assert_columns_close
 
 pytestmark = pytest.mark.gpu
 
 LAYOUTS = ["nan_pad", "big_pad", "off16", "off48", "off240", "unpadded"]
-POISON = 0x7FF8DEADBEEF0001                       # a quiet NaN whose payload no arithmetic produces
-
-
-def fit(n, dtype, layout):
-    """n as the layout can take it: ld = n must be even for the real kind; the complex kind's unpadded case is the odd one"""
-    if layout == "unpadded" and (n % 2 == 1) != (np.dtype(dtype).kind == "c"):
-        return n + 1
-    return n
-
-
-class CallerPanel:
-    """An n x ncols panel wrapped (lk_basis_wrap) inside one flat engine-owned buffer laid out as `layout` says.  `set` writes panel
-    contents, `get` reads them back and asserts that nothing outside the panel's rows changed."""
-
-    def __init__(self, ctx, dtype, n, ncols, layout, seed=0):
-        dt = np.dtype(dtype)
-        cplx = dt.kind == "c"
-        es = dt.itemsize
-        if layout == "unpadded":
-            assert (n % 2 == 1) == cplx, "fit() the size first"
-            ld, head = n, 16 // es
-        else:
-            ld = n + (3 if cplx else 3 + (n + 3) % 2)
-            head = int(layout[3:]) // es if layout.startswith("off") else 0
-        total = head + ld * ncols + 64
-        img = np.empty(total, dtype=dt)
-        if layout in ("nan_pad", "unpadded"):
-            img.view(np.uint64)[:] = POISON
-        elif layout == "big_pad":
-            img.view(np.float64)[:] = 1e300
-            img.view(np.float64)[1::2] = -1e300
-        else:
-            ora.fill_counter(img, 9000 + seed)
-            img += np.where(img.real >= 0, 0.5, -0.5)              # |live entry| >= 0.5
-        self.inside = np.zeros(total, dtype=bool)
-        for j in range(ncols):
-            self.inside[head + j * ld:head + j * ld + n] = True
-        self.n, self.ncols, self.ld, self.head, self.dtype, self.layout = n, ncols, ld, head, dt, layout
-        self.img = img
-        self.backing = lk.krylov_basis_gpu(total, 1, dt, ctx)
-        self.backing.upload(img.reshape(-1, 1))
-        ptr = self.backing.info()[4] + head * es
-        assert ptr % 16 == 0 and (layout == "nan_pad" or layout == "big_pad" or ptr % 256 != 0)
-        h = C.c_void_p()
-        _capi.check(self.backing._lib.lk_basis_wrap(ctx._h, _capi.LK_C128 if cplx else _capi.LK_F64, n, ncols, ld, C.c_void_p(ptr),
-                                                    C.byref(h)))
-        self.B = lk.krylov_basis_gpu(n, ncols, dt, ctx, _handle=h, _owner=self.backing)
-
-    def _cols(self, buf):
-        return np.stack([buf[self.head + j * self.ld:self.head + j * self.ld + self.n] for j in range(self.ncols)], axis=1)
-
-    def set(self, A, col0=0):
-        A = np.asarray(A, dtype=self.dtype).reshape(self.n, -1, order="F")
-        buf = self.backing.download()[:, 0]
-        for j in range(A.shape[1]):
-            o = self.head + (col0 + j) * self.ld
-            buf[o:o + self.n] = A[:, j]
-        self.backing.upload(buf.reshape(-1, 1))
-
-    def get(self, what=""):
-        buf = self.backing.download()[:, 0]
-        out = ~self.inside
-        got, want = buf[out].view(np.uint64), self.img[out].view(np.uint64)
-        bad = np.flatnonzero(got != want)
-        assert bad.size == 0, (f"{what} [{self.layout}, n = {self.n}, ld = {self.ld}]: {bad.size} words outside the panel changed, first at "
-                               f"outside word {int(bad[0])}: {got[bad[0]]:#x} (was {want[bad[0]]:#x})")
-        return np.asfortranarray(self._cols(buf))
 
 
 _CTXS = {}

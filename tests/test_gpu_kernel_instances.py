@@ -15,56 +15,14 @@ import numpy as np
 import pytest
 
 import lightkrylov_amd as lk
-from tests._gpu_helpers import KINDS, basis, seeded, orthonormal_basis
+from tests._gpu_helpers import KINDS, basis, check_entrywise, ext, is_cplx, orthonormal_basis, product_scale, seeded
 from tests._tol import _report
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -53
 DEFAULTS = dict(grid_mult=2, blas1_grid_mult=2, cw_u=0, cw_grid_mult=3, dot_colwise=1, xhy_db=1, gram_rs=1, gemm_3m=1, gemm_roll=1,
                 gemm_mfma_min=0, store_policy=2, store_split=0, recompute_update=1, pool_slab_cols=160, csr_stream=1, wide_s3=1,
                 wide_regs=2, async_arnoldi=1)
-
-
-def gamma(m):
-    """gamma_m of the double sum plus that of the longdouble reference (u = 2^-64), which is not exact either: a row of one product
-    rounds by up to u of it, so the measured ratio can come within 2 % of 1"""
-    m = np.asarray(m, dtype=np.float64)
-    return m * U / (1.0 - m * U) + m * 2.0 ** -64 / (1.0 - m * 2.0 ** -64)
-
-
-def is_cplx(dtype):
-    return np.dtype(dtype).kind == "c"
-
-
-def ext(A):
-    A = np.asarray(A)
-    return A.astype(np.clongdouble) if np.iscomplexobj(A) else A.astype(np.longdouble)
-
-
-def product_scale(A, B):
-    """|A| |B| (real) or (|Ar|+|Ai|)(|Br|+|Bi|) (complex): the scale of the bound; A, B already in the orientation of the product"""
-    if np.iscomplexobj(A) or np.iscomplexobj(B):
-        return (np.abs(A.real) + np.abs(A.imag)) @ (np.abs(B.real) + np.abs(B.imag))
-    return np.abs(A) @ np.abs(B)
-
-
-def check_entrywise(got, ref, scale, m, cplx, label):
-    """entrywise |got - ref| against the bound for sums of m terms (m: scalar or array broadcast like got); returns the worst ratio"""
-    got = np.asarray(got)
-    bound = (2.0 * gamma(2 * np.asarray(m) + 5) if cplx else gamma(m)) * scale
-    d = got.astype(ref.dtype) - ref
-    errs = [np.abs(d.real), np.abs(d.imag)] if cplx else [np.abs(d)]
-    ratio = 0.0
-    for e in errs:
-        e = e.astype(np.float64)
-        over = e > bound
-        assert not over.any(), f"{label}: entry {np.argwhere(over)[0].tolist()} off by {e[over][0]:.3e} > bound {bound[over][0]:.3e}"
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r = np.where(bound > 0, e / np.where(bound > 0, bound, 1.0), 0.0)
-        ratio = max(ratio, float(r.max()) if r.size else 0.0)
-    _report(label, ratio, 1.0, "entrywise gamma bound")
-    return ratio
 
 
 def check_xhy(got, X, Y, label):
