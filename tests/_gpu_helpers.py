@@ -1,11 +1,13 @@
 """Shared helpers of the GPU test files (test infrastructure: inputs come from the oracle's counter RNG, so CPU and GPU see identical data)."""
 import ctypes as C
 import functools
+import threading
 
 import numpy as np
 
 import lightkrylov_amd as lk
 from lightkrylov_amd import _capi
+from lightkrylov_amd.context import _DevMem
 from oracle import oracle as ora
 from tests._tol import _report
 
@@ -250,3 +252,140 @@ class CallerPanel:
         assert bad.size == 0, (f"{what} [{self.layout}, n = {self.n}, ld = {self.ld}]: {bad.size} words outside the panel changed, first at "
                                f"outside word {int(bad[0])}: {got[bad[0]]:#x} (was {want[bad[0]]:#x})")
         return np.asfortranarray(self._cols(buf))
+
+
+# ---- row-sharded emulation on one GPU (tests/test_gpu_sharded_emulation.py describes it) --------------------------------------------
+class _EmulatedGroup:
+    """Sum all-reduce between `nranks` threads; buffers live on the same device."""
+
+    def __init__(self, nranks):
+        import torch
+        self.torch = torch
+        self.n = nranks
+        self.barrier = threading.Barrier(nranks)
+        self.slots = [None] * nranks
+        self.calls = 0
+        self.rank_calls = [0] * nranks                  # all-reduce calls each rank made (they must agree)
+
+    def hook(self, rank, ctx):
+        torch = self.torch
+
+        def _cb(_user, dev_ptr, count, stream_ptr):
+            try:
+                self.rank_calls[rank] += 1
+                ctx.sync_stream_only()
+                self.slots[rank] = torch.as_tensor(_DevMem(int(dev_ptr), int(count)), device="cuda:0")
+                self.barrier.wait(timeout=120)
+                if rank == 0:
+                    total = self.slots[0].clone()
+                    for r in range(1, self.n):
+                        total += self.slots[r]
+                    for r in range(self.n):
+                        self.slots[r].copy_(total)
+                    torch.cuda.synchronize()
+                    self.calls += 1
+                self.barrier.wait(timeout=120)
+                return 0
+            except Exception as exc:  # noqa: BLE001
+                print("emulated all-reduce failed:", repr(exc))
+                self.barrier.abort()
+                return 1
+        return _capi.ALLREDUCE_FN(_cb)
+
+
+def _sharded(n, nranks, body):
+    """Run body(rank, ctx, row0, n_local) on `nranks` threads with an emulated all-reduce; returns results."""
+    lib = _capi.load()
+    grp = _EmulatedGroup(nranks)
+    out, errs = [None] * nranks, []
+
+    def worker(rank):
+        try:
+            ctx = lk.Context(device=0, use_torch_stream=False)           # own stream per rank
+            ctx.sync_stream_only = lambda: _capi.check(lib.lk_sync(ctx._h))
+            cb = grp.hook(rank, ctx)
+            _capi.check(lib.lk_set_allreduce(ctx._h, cb, None, nranks, rank))
+            ctx._cb, ctx.nranks, ctx.rank = cb, nranks, rank
+            row0, nl = lk.row_partition(n, nranks, rank)
+            ctx.set_partition(row0, n)
+            out[rank] = body(rank, ctx, row0, nl)
+        except Exception as exc:  # noqa: BLE001
+            errs.append(exc)
+            grp.barrier.abort()
+
+    ts = [threading.Thread(target=worker, args=(r,)) for r in range(nranks)]
+    [t.start() for t in ts]
+    [t.join(600) for t in ts]
+    assert not errs, errs
+    return out, grp
+
+
+# ---- bases wider than 512 columns (tests/test_oracle_very_wide.py pins these inputs, tests/test_gpu_very_wide_bases.py runs them) --------
+# lk_dgs changes schedule at 512 | 513 (one sweep holds 512 columns), runs 2 / 3 / 4 device panels of 512 up to 2048 and panels of 128
+# with a host round trip each beyond: both sides of every panel count, 2176 = 17 * 128 (a full last panel), 2177 (a last panel of one)
+VERY_WIDE_K = (512, 513, 1023, 1024, 1025, 1536, 1537, 2047, 2048, 2049, 2100, 2176, 2177)
+VERY_WIDE_FLAG_K = (600, 1600, 2100)              # one k per schedule for the flags and outputs
+VERY_WIDE_PANEL_K = (1030, 2060)                  # caller-owned panels, sharded emulation, one step of each factorisation
+VERY_WIDE_BLOCK_K = (600, 1100)                   # lk_dgs_block's column-by-column route
+
+
+def very_wide_n(k):
+    """the smallest odd n >= k + 11: a skewed (near orthonormal) panel needs n >= k, and an odd n leaves every row tile ragged"""
+    n = k + 11
+    return n if n % 2 == 1 else n + 1
+
+
+def step_longdouble(v, X):
+    """(beta = h1 + h2, ||y''||, y'' / ||y''||) of one two-pass step in longdouble"""
+    h1, h2, _y1, y2 = dgs_longdouble(v, X)
+    nrm = np.sqrt((y2.conj() @ y2).real)
+    return h1 + h2, nrm, y2 / nrm
+
+
+def arnoldi_step_longdouble(d, X):
+    """column k of H (k + 1 entries) and x_(k+1) of the Arnoldi step on diag(d) from the k columns of X (arnoldi.fypp:36-62)"""
+    h, beta, x = step_longdouble(_long(d) * _long(X[:, -1]), X)
+    return np.concatenate([h, [beta]]), x
+
+
+def lanczos_step_longdouble(d, X):
+    """column k of T (k + 1 entries) and x_(k+1) of the Lanczos step on diag(d): the two local projections in sequence (lanczos.fypp:57-60),
+    the full step whose coefficients are dropped (:62), the norm (:29)"""
+    Xl = _long(X)
+    k = X.shape[1]
+    v = _long(d) * Xl[:, -1]
+    t = np.zeros(k + 1, dtype=Xl.dtype)
+    for i in range(max(1, k - 1), k + 1):
+        t[i - 1] = Xl[:, i - 1].conj() @ v
+        v = v - t[i - 1] * Xl[:, i - 1]
+    _h, beta, x = step_longdouble(v, X)
+    t[k] = beta
+    return t, x
+
+
+def bidiag_step_longdouble(d, U, V):
+    """step k of golub_kahan.fypp:27-52 on diag(d) from the k columns of U and the k - 1 of V: (alpha, v_k, beta, u_(k+1)); A^H = conj(d)"""
+    dl = _long(d)
+    _h, alpha, v = step_longdouble(dl.conj() * _long(U[:, -1]), V)
+    _h, beta, u = step_longdouble(dl * v, U)
+    return alpha, v, beta, u
+
+
+def arnoldi_block_step_longdouble(d, X, p):
+    """the kp x p block of H, the p x p factor R and the p new columns of the block Arnoldi step on diag(d) from the kp columns of X
+    (arnoldi.fypp:39-55): p products, the block step column by column, qr_no_pivoting of the new block (qr.fypp:129-165)"""
+    Xl = _long(X)
+    kp = X.shape[1]
+    W = _long(d)[:, None] * Xl[:, kp - p:]
+    Hb = np.zeros((kp, p), dtype=Xl.dtype)
+    for j in range(p):
+        h1, h2, _y1, W[:, j] = dgs_longdouble(W[:, j], X)
+        Hb[:, j] = h1 + h2
+    R = np.zeros((p, p), dtype=Xl.dtype)
+    for j in range(p):
+        if j > 0:
+            h1, h2, _y1, W[:, j] = dgs_longdouble(W[:, j], W[:, :j])
+            R[:j, j] = h1 + h2
+        R[j, j] = np.sqrt((W[:, j].conj() @ W[:, j]).real)
+        W[:, j] = W[:, j] / R[j, j]
+    return Hb, R, W

@@ -13,72 +13,10 @@ import pytest
 import lightkrylov_amd as lk
 from lightkrylov_amd import _capi
 from lightkrylov_amd.context import _DevMem
+from tests._gpu_helpers import _EmulatedGroup, _sharded
 from tests._tol import assert_close
 
 pytestmark = pytest.mark.gpu
-
-
-class _EmulatedGroup:
-    """Sum all-reduce between `nranks` threads; buffers live on the same device."""
-
-    def __init__(self, nranks):
-        import torch
-        self.torch = torch
-        self.n = nranks
-        self.barrier = threading.Barrier(nranks)
-        self.slots = [None] * nranks
-        self.calls = 0
-
-    def hook(self, rank, ctx):
-        torch = self.torch
-
-        def _cb(_user, dev_ptr, count, stream_ptr):
-            try:
-                ctx.sync_stream_only()
-                self.slots[rank] = torch.as_tensor(_DevMem(int(dev_ptr), int(count)), device="cuda:0")
-                self.barrier.wait(timeout=120)
-                if rank == 0:
-                    total = self.slots[0].clone()
-                    for r in range(1, self.n):
-                        total += self.slots[r]
-                    for r in range(self.n):
-                        self.slots[r].copy_(total)
-                    torch.cuda.synchronize()
-                    self.calls += 1
-                self.barrier.wait(timeout=120)
-                return 0
-            except Exception as exc:  # noqa: BLE001
-                print("emulated all-reduce failed:", repr(exc))
-                self.barrier.abort()
-                return 1
-        return _capi.ALLREDUCE_FN(_cb)
-
-
-def _sharded(n, nranks, body):
-    """Run body(rank, ctx, row0, n_local) on `nranks` threads with an emulated all-reduce; returns results."""
-    lib = _capi.load()
-    grp = _EmulatedGroup(nranks)
-    out, errs = [None] * nranks, []
-
-    def worker(rank):
-        try:
-            ctx = lk.Context(device=0, use_torch_stream=False)           # own stream per rank
-            ctx.sync_stream_only = lambda: _capi.check(lib.lk_sync(ctx._h))
-            cb = grp.hook(rank, ctx)
-            _capi.check(lib.lk_set_allreduce(ctx._h, cb, None, nranks, rank))
-            ctx._cb, ctx.nranks, ctx.rank = cb, nranks, rank
-            row0, nl = lk.row_partition(n, nranks, rank)
-            ctx.set_partition(row0, n)
-            out[rank] = body(rank, ctx, row0, nl)
-        except Exception as exc:  # noqa: BLE001
-            errs.append(exc)
-            grp.barrier.abort()
-
-    ts = [threading.Thread(target=worker, args=(r,)) for r in range(nranks)]
-    [t.start() for t in ts]
-    [t.join(600) for t in ts]
-    assert not errs, errs
-    return out, grp
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.complex128])
