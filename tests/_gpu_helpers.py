@@ -57,6 +57,13 @@ def check_entrywise(got, ref, scale, m, cplx, label):
     return ratio
 
 
+def device_num_cu(c):
+    """the compute-unit count of the context's device, as lk_init reads it (the context has no accessor for it): blas1_grid caps the
+    BLAS-1 grids at num_cu * "blas1_grid_mult" blocks"""
+    import torch
+    return torch.cuda.get_device_properties(c.device).multi_processor_count
+
+
 def seeded(n, dtype, seed):
     x = np.empty(n, dtype=dtype)
     ora.fill_counter(x, seed)

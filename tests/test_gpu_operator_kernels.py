@@ -21,7 +21,7 @@ import lightkrylov_amd as lk
 from lightkrylov_amd import _capi
 from lightkrylov_amd.linops import _engine_linop
 from oracle import oracle as ora
-from tests._gpu_helpers import KINDS, CallerPanel, check_entrywise, ext, is_cplx, product_scale, seeded
+from tests._gpu_helpers import KINDS, CallerPanel, check_entrywise, device_num_cu, ext, is_cplx, product_scale, seeded
 from tests._operator_cases import (BIDIAG_N, BREAKDOWN_M, CSR_STREAM_N, DENSE_N, DIAG_N, GL_CASES, GL_RTOL, LAP5_N, LINSPACE_ROW0, breakdown_cases,
                                    check_complex_diag, csr_conj_transpose, csr_longdouble, csr_stream_case, dense_case, dense_with_lda,
                                    diag_case, lap5_input, lap5_longdouble, linspace_diag_exact, oracle_bidiag_breakdown, oracle_breakdown)
@@ -161,10 +161,8 @@ def test_ginzburg_landau_step_around_the_block_edge(kctx, n, nsub):
 def _diag_big_n(c):
     """an odd size above 2 * num_cu * blas1_grid_mult * 256 16-byte lanes: every thread of the capped grid runs the two-element loop of
     k_diag_linspace, some its tail loop too, and the odd last element is on its own.  The compute-unit count is that of the context's
-    device, as lk_init reads it (the context has no accessor for it)."""
-    import torch
-    num_cu = torch.cuda.get_device_properties(c.device).multi_processor_count
-    return 2 * (2 * num_cu * BLAS1_GRID_MULT * 256 + 77) + 1
+    device (tests/_gpu_helpers.py: device_num_cu)."""
+    return 2 * (2 * device_num_cu(c) * BLAS1_GRID_MULT * 256 + 77) + 1
 
 
 @pytest.mark.parametrize("dtype", KINDS)
