@@ -184,7 +184,7 @@ int lk_lazy_speculation_stats(lk_context_t ctx, int64_t *out2);
  * step of lk_arnoldi run double_gram_schmidt_step (gram_schmidt.fypp:12-57) AND qr_no_pivoting's norm + scale (qr.fypp:135-165) as ONE
  * persistent kernel: each block keeps its rows for the three phases, the phases' sums meet inside the launch in a fixed order.  Panels
  * up to the register files' capacity (64 MB on the chip) stay IN REGISTERS for the whole step: X is read once, k + 2 columns of
- * traffic instead of 3k + 5.  Tuning keys: "resident" (default 1; 0 = always the three-sweep schedule), "resident_max_mb" (default 192:
+ * traffic instead of 3k + 5.  Tuning keys: "resident" (default 1; 0 = always the three-sweep schedule), "resident_max_mb" (default 320:
  * MB of panel the single launch takes), "resident_onchip" (default 1; 0 = never the register-resident kernel), "resident_rev" (tile
  * order of the cache-resident kernel's phase 2) and "resident_spin_ms" (default 50: bound on the first grid-wide wait, which normally ends within microseconds -- 0 = give up there at
  * once, the tests' way to the fallback --; a launch that cannot get all its blocks on the chip, e.g. because another context's persistent

@@ -755,11 +755,13 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
     // coefficients of the earlier ones in it), and then at once to what the fused block pass needs (two partial blocks per CU), so that no pass has to grow it again
     auto ensure = [&](int64_t blocks) -> int {
         int64_t need = 2 * sect + npart_n + blocks * nslots;
+        // (the fused pass's share counts BEFORE the early return: on a panel of fewer row tiles than CUs this pass needs less than the fused one, and a workspace
+        //  that an earlier, smaller shape had grown could hold this pass and not the next -- k = 64 then 128 with 17 right-hand sides at n = 4099)
+        const int64_t fused = 2 * sect + npart_n + (int64_t)c->num_cu * 2 * nslots;
+        if (may_grow && need < fused) need = fused;
         if (c->xhy_n >= need) return LK_OK;
         if (!may_grow)
             return fail(LK_ERR_INVALID, "internal: xhy workspace too small for a later pass of the block Gram-Schmidt (%lld < %lld)", (long long)c->xhy_n, (long long)need);
-        const int64_t fused = 2 * sect + npart_n + (int64_t)c->num_cu * 2 * nslots;
-        if (need < fused) need = fused;
         if (c->xhy) HIPCHK(hipFree(c->xhy));
         c->xhy = nullptr;
         c->xhy_n = 0;

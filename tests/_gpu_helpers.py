@@ -261,6 +261,83 @@ class CallerPanel:
         return np.asfortranarray(self._cols(buf))
 
 
+# ---- panels whose columns lie further apart than 32-bit offsets reach (tests/test_gpu_far_columns.py) ---------------------------------
+# Column j of a panel starts j * stride bytes from the base.  The three limits of narrowed address arithmetic and the first column
+# that lies at or beyond each (8-byte doubles):
+#   geometry A, stride 2^28 B: 2^32 B = 16 strides -> column 16;  2^31 doubles = 2^34 B -> column 64;   2^32 doubles = 2^35 B -> column 128
+#                              176 columns = 176 * 2^28 B = 44 GiB of address space
+#   geometry B, stride 2^26 B: 2^32 B -> column 64;               2^34 B -> column 256;                 2^35 B -> column 512
+#                              513 columns = 513 * 2^26 B = 32.06 GiB
+FAR_STRIDE_A, FAR_COLS_A = 1 << 28, 176
+FAR_STRIDE_B, FAR_COLS_B = 1 << 26, 513
+FAR_BAND = 4096                                   # bytes of each guard band
+
+
+class FarPanel:
+    """An n x ncols panel wrapped (lk_basis_wrap) at ld = stride_bytes / itemsize inside one torch byte buffer of ncols * stride_bytes:
+    only rows [0, n) of a column are ever touched, so the panel moves megabytes while its columns lie up to 44 GiB from its base.
+    `set` / `get` go through a torch strided view (64-bit strides), never through the engine.  Rows [0, n) of every column start as
+    POISON, the 4 KB after row n of every column and the last 4 KB before the next column are POISON guard bands: `get` asserts
+    that both bands of every column are bit-identical and returns ALL columns; `shadow` is what was set, for the columns a call must
+    not write.  `backing`: a buffer to reuse (one allocation per geometry and module)."""
+
+    def __init__(self, ctx, dtype, n, ncols, stride_bytes, backing=None):
+        import torch
+        dt = np.dtype(dtype)
+        es = dt.itemsize
+        assert stride_bytes % (32 * es) == 0 and n * es + 2 * FAR_BAND <= stride_bytes
+        if backing is None:
+            backing = torch.empty(ncols * stride_bytes, dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        assert backing.numel() >= ncols * stride_bytes and backing.data_ptr() % 256 == 0
+        self.backing, self.torch = backing, torch
+        self.n, self.ncols, self.stride, self.dtype, self.ld = n, ncols, stride_bytes, dt, stride_bytes // es
+        self.words = backing[:ncols * stride_bytes].view(torch.int64).view(ncols, stride_bytes // 8)       # one row per column
+        nw, bw = n * es // 8, FAR_BAND // 8
+        self._rows = self.words[:, :nw]
+        self._bands = (self.words[:, nw:nw + bw], self.words[:, -bw:])
+        self._rows.fill_(POISON)                                        # (below 2^63: the pattern is a positive 64-bit word)
+        for b in self._bands:
+            b.fill_(POISON)
+        torch.cuda.synchronize()
+        img = np.empty((ncols, n), dtype=dt)
+        img.view(np.uint64)[...] = POISON
+        self.shadow = img.T                                             # (n x ncols, column-major)
+        h = C.c_void_p()
+        lib = _capi.load()
+        _capi.check(lib.lk_basis_wrap(ctx._h, _capi.LK_C128 if dt.kind == "c" else _capi.LK_F64, n, ncols, self.ld,
+                                      C.c_void_p(backing.data_ptr()), C.byref(h)))
+        self.B = lk.krylov_basis_gpu(n, ncols, dt, ctx, _handle=h, _owner=backing)
+
+    def set(self, A, col0=0):
+        A = np.asarray(A, dtype=self.dtype).reshape(self.n, -1, order="F")
+        m = A.shape[1]
+        host = np.ascontiguousarray(A.T).view(np.int64).reshape(m, -1)                                 # one row per column
+        self.B.ctx.sync()
+        self._rows[col0:col0 + m].copy_(self.torch.from_numpy(host))
+        self.torch.cuda.synchronize()
+        self.shadow[:, col0:col0 + m] = A
+
+    def get(self, what=""):
+        self.B.ctx.sync()
+        self.torch.cuda.synchronize()
+        for name, b in zip(("after row n", "before the next column"), self._bands):
+            w = b.contiguous().cpu().numpy().view(np.uint64)
+            bad = np.argwhere(w != POISON)
+            assert bad.size == 0, (f"{what}: guard band {name} of column {int(bad[0][0])} changed at word {int(bad[0][1])}: "
+                                   f"{int(w[tuple(bad[0])]):#x}")
+        rows = self._rows.contiguous().cpu().numpy()
+        return np.asfortranarray(rows.view(self.dtype).T)
+
+    def assert_untouched(self, got, written, what=""):
+        """every column of `got` outside `written` is bit-identical with what was set (a store whose offset wrapped modulo 2^32 bytes
+        or doubles lands on the same row of a lower column)"""
+        keep = np.setdiff1d(np.arange(self.ncols), np.asarray(list(written), dtype=np.int64))
+        a, b = (np.ascontiguousarray(M.T[keep]).view(np.uint64) for M in (got, self.shadow))           # one row per column
+        bad = np.argwhere(a != b)
+        assert bad.size == 0, (f"{what}: column {int(keep[bad[0][0]])} (not an output) changed at row "
+                               f"{int(bad[0][1]) // (self.dtype.itemsize // 8)}")
+
+
 # ---- row-sharded emulation on one GPU (tests/test_gpu_sharded_emulation.py describes it) --------------------------------------------
 class _EmulatedGroup:
     """Sum all-reduce between `nranks` threads; buffers live on the same device."""

@@ -7,7 +7,8 @@ Here the panel lies inside a larger buffer whose rows outside [0, n) of every co
   big_pad   the same with +-1e300 (a read of it swamps the result, a square of it overflows);
   offNNN    the panel starts NNN bytes (16, 48, 240: 16-byte but not 256-byte aligned) into the buffer, with live non-zero rows above it,
             between its columns and below it -- a sharded caller's layout;
-  unpadded  ld = n (real kind: n even, complex kind: n odd), 16 bytes of NaN above and NaN below: no column starts on a 256-byte grid.
+  unpadded  ld = n (real kind: n even, complex kind: n odd), 16 bytes of NaN above and NaN below: no column starts on a 256-byte grid;
+  far columns  ld = 2^26 or 2^28 bytes' worth of elements, columns beyond 2^32 bytes, 2^31 and 2^32 doubles from the base: tests/test_gpu_far_columns.py.
 
 Every result is compared with the oracle, and every row of the buffer outside [0, n) of the panel must be BIT-identical after the call."""
 import ctypes as C
