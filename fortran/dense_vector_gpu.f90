@@ -60,6 +60,7 @@ module lightkrylov_gpu
     public :: gpu_arnoldi_rdp, gpu_arnoldi_cdp
     public :: gpu_arnoldi_segments_rdp, gpu_arnoldi_segments_cdp, lk_gpu_progress
     public :: gpu_lanczos_rdp, gpu_lanczos_cdp, gpu_bidiag_rdp, gpu_bidiag_cdp, gpu_qr_rdp, gpu_qr_cdp
+    public :: gpu_kexpm_rdp, gpu_kexpm_cdp
 
     type(c_ptr), save :: ctx = c_null_ptr
     integer(c_int64_t), save :: part_row0 = 0          ! first global row of this rank's block (lk_gpu_set_partition)
@@ -963,5 +964,38 @@ contains
         call c_f_pointer(c_loc(R), Rr, [2*size(R)])
         call chk(lk_qr(Q, c0, int(size(R, 2), c_int), Rr, int(size(R, 1), c_int64_t), tl, cinfo), 'gpu_qr_cdp')
         info = cinfo
+    end subroutine
+
+    !> kexpm, vector form (src/Expm/ExpmLib.fypp:128-232) as ONE engine call (lk_kexpm): column jc (0-based) of the panel Bc becomes
+    !> exp(tau op(A)) times column jb of Bb.  X: the caller's workspace panel of at least kdim + 1 columns (kdim defaults to the
+    !> reference's 100), reused from call to call by a time stepper; it returns holding the Krylov basis.  info as in the reference:
+    !> kp > 0 converged with kp Krylov vectors, -1 not converged in kdim steps.  krylov_exptA (:365-392) is tol = atol_dp, kdim = 30.
+    !> The handles carry the kind: the two names exist for symmetry with the other wrappers.
+    subroutine gpu_kexpm_rdp(Bc, jc, op, Bb, jb, X, tau, tol, info, trans, kdim, err_est)
+        type(c_ptr), intent(in) :: Bc, op, Bb, X
+        integer, intent(in) :: jc, jb
+        real(dp), intent(in) :: tau, tol
+        integer, intent(out) :: info
+        logical, optional, intent(in) :: trans
+        integer, optional, intent(in) :: kdim
+        real(dp), optional, intent(out) :: err_est
+        integer(c_int) :: cinfo, tr, nk
+        real(c_double) :: err
+        tr = 0; if (present(trans)) tr = merge(1, 0, trans)
+        nk = 100; if (present(kdim)) nk = kdim                                ! kmax, ExpmLib.fypp:149
+        call chk(lk_kexpm(op, tr, Bb, int(jb, c_int), Bc, int(jc, c_int), X, tau, tol, nk, cinfo, err), 'gpu_kexpm')
+        info = cinfo
+        if (present(err_est)) err_est = err
+    end subroutine
+
+    subroutine gpu_kexpm_cdp(Bc, jc, op, Bb, jb, X, tau, tol, info, trans, kdim, err_est)
+        type(c_ptr), intent(in) :: Bc, op, Bb, X
+        integer, intent(in) :: jc, jb
+        real(dp), intent(in) :: tau, tol
+        integer, intent(out) :: info
+        logical, optional, intent(in) :: trans
+        integer, optional, intent(in) :: kdim
+        real(dp), optional, intent(out) :: err_est
+        call gpu_kexpm_rdp(Bc, jc, op, Bb, jb, X, tau, tol, info, trans, kdim, err_est)
     end subroutine
 end module lightkrylov_gpu

@@ -491,6 +491,25 @@ module lightkrylov_hip_c
             integer(c_int), intent(out) :: info
             integer(c_int) :: rc
         end function
+        !> expm(A) of a small dense matrix on the host (stdlib_linalg's expm, ExpmLib.fypp:12, 207); dtype = LK_F64 / LK_C128, lda / lde in elements
+        function lk_expm_dense(dtype, n, A, lda, E, lde) bind(C, name="lk_expm_dense") result(rc)
+            import :: c_int, c_double, c_int64_t
+            integer(c_int), value :: dtype, n
+            real(c_double), intent(in) :: A(*)
+            integer(c_int64_t), value :: lda, lde
+            real(c_double), intent(inout) :: E(*)
+            integer(c_int) :: rc
+        end function
+        !> kexpm, vector form (ExpmLib.fypp:128-232): column jc of Bc = exp(tau op(A)) (column jb of Bb); X = workspace of >= kdim + 1 columns
+        function lk_kexpm(A, trans, Bb, jb, Bc, jc, X, tau, tol, kdim, info, err_est) bind(C, name="lk_kexpm") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: A, Bb, Bc, X
+            integer(c_int), value :: trans, jb, jc, kdim
+            real(c_double), value :: tau, tol
+            integer(c_int), intent(out) :: info
+            real(c_double), intent(out) :: err_est
+            integer(c_int) :: rc
+        end function
     end interface
 
 contains

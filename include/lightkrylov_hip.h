@@ -463,6 +463,32 @@ int lk_qr(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, double tol, int *
 int lk_arnoldi_block(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int blksize, int kstart, int kend, double tol, int trans,
                      int *info);
 
+/* ---- matrix exponential: exp(tau A) b by Krylov projection (src/Expm/ExpmLib.fypp) -------------------------------
+ * expm(A) of stdlib_linalg, which ExpmLib.fypp:12, 207 applies to the small projected matrix: E = exp(A) for an n x n column-major
+ * matrix of `dtype` (LK_F64 / LK_C128; lda, lde in elements; E may be A).  HOST ONLY -- no context, no device, no LAPACK: scaling
+ * and squaring with the [13/13] Pade approximant (Higham 2005) and an LU factorisation with partial pivoting (csrc/lk_expm.h).
+ * n = 0 is LK_OK; n < 0, a null pointer or a leading dimension below n is LK_ERR_INVALID. */
+int lk_expm_dense(int dtype, int n, const double *A, int64_t lda, double *E, int64_t lde);
+/* kexpm(c, A, b, tau, tol, info, trans, kdim), vector form: src/Expm/ExpmLib.fypp:128-232 (krylov_exptA, :365-392, is this call
+ * with tol = atol_dp and kdim = 30).  c = column jc of Bc (overwritten) ~ exp(tau op(A)) b, b = column jb of Bb (read only).
+ * X: workspace of the CALLER, >= kdim + 1 columns of the same context, dtype and n_local -- the call allocates no device memory (a
+ * time stepper makes it thousands of times); on return it holds the Krylov basis.  1 <= kdim <= min(ncols(X) - 1, 512).
+ * Same `info` and same c as the reference, on another schedule: ||b||^2 stays on the device, where one kernel forms X(:, 1) = b / ||b||
+ * out of place (:186-187 take three passes and a host round trip); the Arnoldi steps (:196, tolerance atol_dp) are enqueued back to back as
+ * in lk_arnoldi_segments and delivered one by one; for each the host evaluates E = expm(tau H(:kp, :kp)), kp = k + 1, and
+ * err_est = |E(kp, 1) beta| (:207, :215) while the device runs ahead -- at most 24 steps, which touch only columns of X the result
+ * does not use -- and stops the factorisation at the first step with err_est <= tol (:218); an Arnoldi breakdown at step k gives
+ * kp = k and err_est = 0 (:200-204, :215).  The projection c = X(:, :kp) (beta E(:kp, 1)) then runs ONCE (:210-211 repeat it after
+ * every step: O(k^2) column passes of which the last survives).  One host synchronisation beyond those of the factorisation.
+ * info = kp when err_est <= tol (after a breakdown too); kp = 1 and c = 0 for b = 0 (:180-184); -1 when kdim steps did not reach
+ * tol -- c is then the kdim-step approximation (:223-231).  err_est may be NULL.
+ * LK_ERR_INVALID, with nothing written: kdim out of range; c a column of X, or the same column as b; b one of the columns
+ * [0, kdim] of X; operator and vectors of different shape, kind or context; a ROW-SHARDED context (nranks > 1).
+ * Not provided: kexpm_mat (:234-363, the block variant, which needs the column-pivoting qr), row-sharded contexts, and the
+ * Newton-Krylov layer built on the propagator. */
+int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int jc, lk_basis_t X, double tau, double tol, int kdim,
+             int *info, double *err_est);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // lk_engine.hip -- host side of the C ABI declared in include/lightkrylov_hip.h.
 // HIP only: there is no CPU code path in this library.
 #include "lk_internal.h"
+#include "lk_expm.h"
 #include "lk_kernels.hip.h"
 #include "lk_resident.hip.h"
 #include <hip/hip_ext.h>
@@ -9,6 +10,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -222,6 +224,7 @@ struct lk_context_s {
     // asynchronous Arnoldi pipeline (lk_arnoldi): per-step result slots + device-side breakdown flag
     int *stop_dev = nullptr;               // device int: 0, or the step that asked every later step to stop
     int *stop_host = nullptr;              // pinned mirror
+    double *expm_host = nullptr;           // pinned: b^H b of lk_kexpm (2 doubles), copied behind the dot that opens the call
     int *seg_stop_host = nullptr;          // pinned: the stop flag as it stood after each segment of a segmented batch (lk_arnoldi_segments)
     std::vector<hipEvent_t> seg_events;    // ... and the event recorded behind each segment's copies
     int seg_cap = 0;
@@ -1291,10 +1294,10 @@ int materialise_queue(lk_context_t c) {
         ProfScope ps(c, "blas1", (double)q.Bx->n * q.Bx->ed() * 24.0);
         if (cp)
             hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], q.coef[1], q.Bx->col(q.j0), b, 0.0,
-                               T, q.Bx->n, blas1_nt(q.Bx));
+                               T, q.Bx->n, blas1_nt(q.Bx), (const double *)nullptr);
         else
             hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], 0.0, q.Bx->col(q.j0), b, 0.0, T,
-                               q.Bx->n, blas1_nt(q.Bx));
+                               q.Bx->n, blas1_nt(q.Bx), (const double *)nullptr);
         HIPCHK(hipGetLastError());
         return LK_OK;
     }
@@ -1576,6 +1579,7 @@ int lk_init(int device, void *stream, lk_context_t *ctx) {
         HIPCHK(hipMalloc((void **)&c->stop_dev, sizeof(int)));
         HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
         HIPCHK(hipHostMalloc((void **)&c->stop_host, sizeof(int), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&c->expm_host, 2 * sizeof(double), hipHostMallocDefault));
         HIPCHK(hipEventCreateWithFlags(&c->coef_ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->coef_ev, c->stream));
         return LK_OK;
@@ -1636,6 +1640,7 @@ int lk_finalize(lk_context_t c) {
     if (c->coef_ev) (void)hipEventDestroy(c->coef_ev);
     if (c->stop_dev) (void)hipFree(c->stop_dev);
     if (c->stop_host) (void)hipHostFree(c->stop_host);
+    if (c->expm_host) (void)hipHostFree(c->expm_host);
     if (c->seg_stop_host) (void)hipHostFree(c->seg_stop_host);
     for (auto e : c->seg_events) (void)hipEventDestroy(e);
     c->seg_events.clear();
@@ -2155,10 +2160,10 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
     ProfScope ps(c, "blas1", (double)Bx->n * Bx->ed() * 24.0);
     if (cp)
         hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], alpha[1], Bx->col(jx),
-                           beta[0], beta[1], By->col(jy), Bx->n, blas1_nt(Bx));
+                           beta[0], beta[1], By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr);
     else
         hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], 0.0, Bx->col(jx),
-                           beta[0], 0.0, By->col(jy), Bx->n, blas1_nt(Bx));
+                           beta[0], 0.0, By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr);
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -4239,6 +4244,136 @@ int lk_arnoldi_segments(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int 
                         int nseg, lk_progress_fn fn, void *user, int *info) {
     if (nseg < 0 || (nseg > 0 && !seg_last)) return fail(LK_ERR_INVALID, "lk_arnoldi_segments: bad segment list");
     return arnoldi_impl(A, X, H, ldh, kstart, kend, tol, trans, info, seg_last, nseg, fn, user);
+}
+
+// ---- exp(tau A) b by Krylov projection (src/Expm/ExpmLib.fypp) ----------------------------------------------------------------------
+int lk_expm_dense(int dtype, int n, const double *A, int64_t lda, double *E, int64_t lde) {
+    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "lk_expm_dense: unknown dtype %d", dtype);
+    if (n < 0) return fail(LK_ERR_INVALID, "lk_expm_dense: n = %d", n);
+    if (n == 0) return LK_OK;
+    if (!A || !E) return fail(LK_ERR_INVALID, "lk_expm_dense: null argument");
+    if (lda < n || lde < n) return fail(LK_ERR_INVALID, "lk_expm_dense: leading dimension below n = %d", n);
+    try {
+        if (dtype == LK_C128)
+            lk_expm::expm(n, reinterpret_cast<const std::complex<double> *>(A), lda, reinterpret_cast<std::complex<double> *>(E), lde);
+        else
+            lk_expm::expm(n, A, lda, E, lde);
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_expm_dense: no host memory for the work arrays of a %d x %d matrix", n, n);
+    }
+    return LK_OK;
+}
+
+namespace {
+// what the progress function of lk_kexpm keeps between the deliveries of the Arnoldi steps
+struct KexpmState {
+    int ED = 1;
+    const double *H = nullptr;        // (ldh x kdim + 1), zeroed before the first step
+    int64_t ldh = 0;
+    double tau = 0.0, tol = 0.0;
+    const double *s_host = nullptr;   // pinned: b^H b, on the host before the first delivery
+    const int *ainfo = nullptr;       // arnoldi's info: set to k BEFORE step k is reported when that step broke down
+    std::vector<double> S, E;         // tau H(:kp, :kp) and its exponential, packed
+    int kp = 0;                       // size of the last approximation
+    double err = 0.0;                 // its error estimate
+    int rc = LK_OK;
+};
+
+// ExpmLib.fypp:199-218 for step k, without the projection: kp, E(:kp, 1) and err_est
+int kexpm_progress(void *user, int kfirst, int klast) {
+    KexpmState &st = *static_cast<KexpmState *>(user);
+    const int ED = st.ED;
+    const double beta = std::sqrt(std::fabs(st.s_host[0]));
+    for (int k = kfirst; k <= klast; ++k) {
+        const bool breakdown = *st.ainfo == k;                   // :200-204 (the last step reported, then)
+        const int kp = breakdown ? k : k + 1;
+        for (int j = 0; j < kp; ++j)
+            for (int i = 0; i < kp * ED; ++i) st.S[((size_t)j * kp) * ED + i] = st.tau * st.H[(size_t)j * st.ldh * ED + i];
+        st.rc = lk_expm_dense(ED == 2 ? LK_C128 : LK_F64, kp, st.S.data(), kp, st.E.data(), kp);   // :207
+        if (st.rc != LK_OK) return 1;
+        const double e = ED == 2 ? std::hypot(st.E[(size_t)(kp - 1) * 2], st.E[(size_t)(kp - 1) * 2 + 1]) : std::fabs(st.E[kp - 1]);
+        st.kp = kp;
+        st.err = breakdown ? 0.0 : e * beta;                     // :215
+        if (st.err <= st.tol) return 1;                          // :218
+    }
+    return 0;
+}
+
+// the device range [lo, hi) of columns [j0, j1) of a panel, rows [0, n)
+bool overlaps(const double *p, lk_basis_t B, int j0, int j1) {
+    const double *lo = B->col(j0), *hi = B->col(j1 - 1) + B->n * B->ed();
+    return p + B->n * B->ed() > lo && p < hi;
+}
+}  // namespace
+
+int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int jc, lk_basis_t X, double tau, double tol, int kdim,
+             int *info, double *err_est) {
+    if (!A || !X || !info) return fail(LK_ERR_INVALID, "lk_kexpm: null argument");
+    LKCHK(check_vec(Bb, jb, "lk_kexpm(b)"));
+    LKCHK(check_vec(Bc, jc, "lk_kexpm(c)"));
+    LKCHK(check_pair(Bb, X, "lk_kexpm(b, X)"));
+    LKCHK(check_pair(Bc, X, "lk_kexpm(c, X)"));
+    lk_context_t c = X->ctx;
+    if (A->ctx != c || A->dtype != X->dtype || A->n != X->n) return fail(LK_ERR_INVALID, "lk_kexpm: operator/vector mismatch");
+    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_kexpm: row-sharded contexts (nranks = %d) are not supported", c->nranks);
+    const int kmax = X->ncols - 1 < KMAX_WIDE ? X->ncols - 1 : KMAX_WIDE;
+    if (kdim < 1 || kdim > kmax)
+        return fail(LK_ERR_INVALID, "lk_kexpm: kdim = %d outside [1, %d] (the workspace has %d columns; at most %d steps)", kdim, kmax, X->ncols, KMAX_WIDE);
+    const double *b = Bb->col(jb);
+    double *cv = Bc->col(jc);
+    if (overlaps(cv, X, 0, X->ncols)) return fail(LK_ERR_INVALID, "lk_kexpm: c is a column of the workspace X");
+    if (cv == b) return fail(LK_ERR_INVALID, "lk_kexpm: c and b are the same column");
+    if (overlaps(b, X, 0, kdim + 1)) return fail(LK_ERR_INVALID, "lk_kexpm: b is one of the workspace columns the call writes");
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    const int ED = X->ed();
+    *info = 0;
+
+    // ||b||^2 stays on the device: k_axpby reads it there and writes X(:, 0) = b / ||b|| out of place (beta = 0: X(:, 0) is not read);
+    // the host gets its copy with the first delivery of the Arnoldi batch
+    LKCHK(dot_device(Bb, jb, Bb, jb, c->red));
+    HIPCHK(hipMemcpyAsync(c->expm_host, c->red, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    X->touch(0);
+    {
+        const int64_t nv = X->n * ED / 2 + 1;
+        ProfScope ps(c, "blas1", (double)X->n * ED * 16.0);
+        if (ED == 2)
+            hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X),
+                               (const double *)c->red);
+        else
+            hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X),
+                               (const double *)c->red);
+        HIPCHK(hipGetLastError());
+    }
+
+    // Arnoldi steps 1..kdim, delivered one by one (ExpmLib.fypp:196 calls arnoldi with its default tolerance)
+    const int64_t ldh = X->ncols;
+    std::vector<double> H((size_t)ldh * (kdim + 1) * ED, 0.0);
+    std::vector<int> segs(kdim);
+    for (int k = 0; k < kdim; ++k) segs[k] = k + 1;
+    int ainfo = 0;
+    KexpmState st;
+    st.ED = ED; st.H = H.data(); st.ldh = ldh; st.tau = tau; st.tol = tol; st.s_host = c->expm_host; st.ainfo = &ainfo;
+    st.S.resize((size_t)(kdim + 1) * (kdim + 1) * ED);
+    st.E.resize((size_t)(kdim + 1) * (kdim + 1) * ED);
+    LKCHK(arnoldi_impl(A, X, H.data(), ldh, 1, kdim, ATOL_DP, trans, &ainfo, segs.data(), kdim, kexpm_progress, &st));
+    LKCHK(st.rc);
+    const double beta = std::sqrt(std::fabs(c->expm_host[0]));
+    if (!std::isfinite(beta)) return fail(LK_ERR_NAN, "lk_kexpm: |b| is not finite");
+    if (st.kp < 1) return fail(LK_ERR_INVALID, "internal: lk_kexpm saw no Arnoldi step");
+    if (beta == 0.0) {                                           // input is zero => output is zero   ExpmLib.fypp:180-184
+        LKCHK(lk_vec_zero(Bc, jc));
+        st.kp = 1;
+        st.err = 0.0;
+    } else {
+        // c = X(:, :kp) (beta E(:kp, 1)), once (:210-211 form it after every step)
+        std::vector<double> coef((size_t)st.kp * ED);
+        for (int i = 0; i < st.kp * ED; ++i) coef[i] = beta * st.E[i];
+        LKCHK(lk_lincomb(X, st.kp, coef.data(), 1, Bc, jc));
+    }
+    if (err_est) *err_est = st.err;
+    *info = st.err <= tol ? st.kp : -1;                          // :223-231
+    return LK_OK;
 }
 
 }  // extern "C"

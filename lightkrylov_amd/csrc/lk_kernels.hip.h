@@ -3029,9 +3029,19 @@ __global__ __launch_bounds__(256) void k_scal(double *__restrict__ x, int64_t n,
     if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[nd - 1] *= ar;
 }
 
+// inv_sqrt_of != NULL (lk_kexpm's first Krylov vector, with beta = 0): alpha = 1 / sqrt(|*inv_sqrt_of|) read on the device, as k_scal's
+// fused normalise does, but OUT OF PLACE: y = x / ||x|| with ||x||^2 left there by k_dot + finish_partials is one read and one write
+// with no host round trip (the reference's `zero_basis; X(1)%add(b); X(1)%scal(1 / beta)`, ExpmLib.fypp:186-187, is two of each behind
+// a norm on the host).  A norm of zero gives alpha = 0: y = 0, on which the first Arnoldi step breaks down and stops the batch.
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_axpby(double ar, double ai, const double *__restrict__ x, double br,
-                                               double bi, double *__restrict__ y, int64_t n, int nt) {
+                                               double bi, double *__restrict__ y, int64_t n, int nt,
+                                               const double *__restrict__ inv_sqrt_of) {
+    if (inv_sqrt_of) {
+        const double nr = sqrt(fabs(*inv_sqrt_of));
+        ar = nr > 0.0 ? 1.0 / nr : 0.0;
+        ai = 0.0;
+    }
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
     const int64_t nd = n * ED, nv = nd / 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;

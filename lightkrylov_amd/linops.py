@@ -127,6 +127,31 @@ class adjoint_linop(abstract_linop):
         self.A.apply_matvec(vec_in, vec_out)
 
 
+class exptA_linop(abstract_linop):
+    """The exponential propagator exp(tau A) as an operator: matvec / rmatvec are `krylov_exptA` on A / A^H (the reference's
+    `abstract_exptA` procedure, ExpmLib.fypp:39-57, 365-392, behind its LTI, Lyapunov and Riccati integrators and eigs on exp(tau L)).
+    One workspace basis of 31 vectors is allocated at the first application and reused by every later one.  `info` keeps the
+    last application's flag (kp > 0, or -1 when thirty Krylov vectors did not reach atol_dp)."""
+
+    def __init__(self, A: abstract_linop, tau: float):
+        super().__init__()
+        self.A, self.tau = A, float(tau)
+        self.info = 0
+        self._X = None
+
+    def _apply(self, vec_in, vec_out, trans: bool) -> None:
+        from .expm import _workspace, krylov_exptA
+        if self._X is None:
+            self._X = _workspace(vec_in, 31)
+        self.info = krylov_exptA(vec_out, self.A, vec_in, self.tau, trans=trans, _basis=self._X)
+
+    def matvec(self, vec_in, vec_out) -> None:
+        self._apply(vec_in, vec_out, False)
+
+    def rmatvec(self, vec_in, vec_out) -> None:
+        self._apply(vec_in, vec_out, True)
+
+
 class _engine_linop(abstract_linop):
     """An operator implemented by a kernel of the HIP engine."""
 

@@ -269,6 +269,13 @@ int lk_bidiag(void *A, void *U, void *V, double *B, int64_t ldb, int k0, int k1,
 int lk_qr(void *Q, int j0, int p, double *R, int64_t ldr, double tol, int *info) {
     (void)Q; (void)j0; (void)p; (void)R; (void)ldr; (void)tol; (void)info; return fail("lk_qr is not in the mock");
 }
+int lk_expm_dense(int dtype, int n, const double *A, int64_t lda, double *E, int64_t lde) {
+    (void)dtype; (void)n; (void)A; (void)lda; (void)E; (void)lde; return fail("lk_expm_dense is not in the mock");
+}
+int lk_kexpm(void *A, int trans, void *Bb, int jb, void *Bc, int jc, void *X, double tau, double tol, int kdim, int *info, double *err_est) {
+    (void)A; (void)trans; (void)Bb; (void)jb; (void)Bc; (void)jc; (void)X; (void)tau; (void)tol; (void)kdim; (void)info; (void)err_est;
+    return fail("lk_kexpm is not in the mock");
+}
 int lk_comm_get_unique_id(void *id) { memset(id, 0, 128); return LK_OK; }
 int lk_comm_init_rank(mock_ctx *c, int nranks, int rank, const void *id) { (void)c; (void)rank; (void)id; return nranks == 1 ? LK_OK : fail("no collective in the mock"); }
 int lk_comm_info(mock_ctx *c, int *nranks, int *rank) { (void)c; if (nranks) *nranks = 1; if (rank) *rank = 0; return LK_OK; }
