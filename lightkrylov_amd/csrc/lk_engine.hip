@@ -17,6 +17,7 @@
 #include <exception>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -109,16 +110,16 @@ struct lk_context_s {
     int wide_regs = 2;         // wide REGISTER tiles: 1 = 8 waves x 32 / 24 columns for 129..256 real / 129..192 complex basis columns instead of the lane split; 2 = also the lane split on 24-column groups for 257..384 columns; 0 = round 3's shapes
     int cplx_wide = 32;        // complex sweeps with 8 waves x 16 columns per block when k exceeds this (0: never) instead of 16 x 8
     // reduction workspace
-    double *partial = nullptr;  // [(KMAX_FUSED+1)*2][MAX_GRID]
-    double *red = nullptr;      // device results: 3 sections of (KMAX_FUSED+1)*2 doubles
-    double *red_host = nullptr; // pinned mirror
-    double *coef = nullptr;     // device coefficients of the lazy path's pending updates (KMAX_WIDE*2 doubles)
-    double *scratch = nullptr;  // scratch vector (grown on demand), scratch_n doubles
-    int64_t scratch_n = 0;
-    double *lz_red = nullptr, *lz_red_host = nullptr;   // lk_lanczos: per step 4 sections (two local passes x {dot, update})
-    int lz_cap = 0;
-    double *xhy = nullptr;      // panel_xhy_mfma: [2 result sections][norm partials][partials], grown on demand
-    int64_t xhy_n = 0;
+    // (every workspace below is a DevBuf / PinnedBuf: the context owns it, growth releases it first and allocates exactly what was asked for,
+    //  and `delete` of the context releases them all -- lk_finalize holds no list of them)
+    DevBuf<double> partial;       // [(KMAX_FUSED+1)*2][MAX_GRID]
+    DevBuf<double> red;           // device results: 3 sections of (KMAX_FUSED+1)*2 doubles
+    PinnedBuf<double> red_host;   // pinned mirror
+    DevBuf<double> coef;          // device coefficients of the lazy path's pending updates (KMAX_WIDE*2 doubles)
+    DevBuf<double> scratch;       // scratch vector (grown on demand)
+    DevBuf<double> lz_red;        // lk_lanczos: per step 4 sections (two local passes x {dot, update})
+    PinnedBuf<double> lz_red_host;
+    DevBuf<double> xhy;           // panel_xhy_mfma: [2 result sections][norm partials][partials], grown on demand
     // communication
     lk_allreduce_fn allreduce = nullptr;
     void *allreduce_user = nullptr;
@@ -157,11 +158,11 @@ struct lk_context_s {
     bool resident_off = false; // a launch gave up (the device is shared with another persistent kernel): the single launch pauses ...
     int64_t resident_pause = 16;       // ... for this many Gram-Schmidt steps (doubling with every give-up, up to 2^20), then is tried again
     int64_t resident_fallback_steps = 0, resident_retry_at = 0;   // steps run on the three sweeps while paused; the count at which to re-arm
-    unsigned *res_cnt = nullptr;
-    long long *res_tim = nullptr;
-    double *blk_red = nullptr, *blk_red_host = nullptr;   // coefficient sections of the block Gram-Schmidt (lk_dgs_block, lk_arnoldi_block): device + pinned
-    int64_t blk_cap = 0;
-    void *res_gran = nullptr;              // {value, tag} granules of the grid sums
+    DevBuf<unsigned> res_cnt;
+    DevBuf<long long> res_tim;
+    DevBuf<double> blk_red;                // coefficient sections of the block Gram-Schmidt (lk_dgs_block, lk_arnoldi_block): device ...
+    PinnedBuf<double> blk_red_host;        // ... + pinned
+    DevBuf<v2d> res_gran;                  // {value, tag} granules of the grid sums
     unsigned long long res_epoch = 0;      // launches so far (the tag of a launch's granules)
     int64_t resident_stats[3] = {0, 0, 0};   // single launches enqueued, launches that gave up, launches that kept the panel in registers
     int lazy = 0;
@@ -218,21 +219,19 @@ struct lk_context_s {
     int lazy_speculate = 1;              // tuning key: 0 switches the anticipation off
     int64_t fusion_stats[4] = {0, 0, 0, 0};  // fused update+dot sweeps, plain deferred updates, virtual temporaries dropped, materialised
     int64_t spec_stats[2] = {0, 0};          // anticipated first-pass sweeps, of which unused
-    double *coef_host = nullptr;         // pinned staging for queued coefficients
+    PinnedBuf<double> coef_host;         // pinned staging for queued coefficients
     hipEvent_t coef_ev = nullptr;        // completion of the last staging copy
     int64_t lazy_stats[4] = {0, 0, 0, 0};  // dot memo hits, batched dot sweeps, queued axpbys, queue flushes
     // asynchronous Arnoldi pipeline (lk_arnoldi): per-step result slots + device-side breakdown flag
-    int *stop_dev = nullptr;               // device int: 0, or the step that asked every later step to stop
-    int *stop_host = nullptr;              // pinned mirror
-    double *expm_host = nullptr;           // pinned: b^H b of lk_kexpm (2 doubles), copied behind the dot that opens the call
-    int *seg_stop_host = nullptr;          // pinned: the stop flag as it stood after each segment of a segmented batch (lk_arnoldi_segments)
+    DevBuf<int> stop_dev;                  // device int: 0, or the step that asked every later step to stop
+    PinnedBuf<int> stop_host;              // pinned mirror
+    PinnedBuf<double> expm_host;           // pinned: b^H b of lk_kexpm (2 doubles), copied behind the dot that opens the call
+    PinnedBuf<int> seg_stop_host;          // pinned: the stop flag as it stood after each segment of a segmented batch (lk_arnoldi_segments)
     std::vector<hipEvent_t> seg_events;    // ... and the event recorded behind each segment's copies
-    int seg_cap = 0;
     bool guard_on = false;                 // launches carry the guard only inside an asynchronous batch
     int guard_step = 0;
-    double *step_red = nullptr;            // device: nsteps x RED_SECTIONS x RED_SECTION doubles
-    double *step_red_host = nullptr;       // pinned mirror
-    int64_t step_red_cap = 0;              // doubles the two buffers hold
+    DevBuf<double> step_red;               // device: nsteps x RED_SECTIONS x RED_SECTION doubles
+    PinnedBuf<double> step_red_host;       // pinned mirror
     int async_arnoldi = 1;                 // tuning key: 0 = one host round trip per step (the round-1 schedule)
     Guard guard() const { return Guard{guard_on ? stop_dev : nullptr, guard_step}; }
     // column pool (lk_pool_*): slabs handed out to per-object hosts
@@ -266,8 +265,7 @@ struct lk_basis_s {
     int dtype;
     int64_t n, ld;
     int ncols;
-    double *data;
-    bool own;
+    DevBuf<double> data;   // owned (lk_basis_create), or a view of caller memory / of some columns of another panel
     int hwm = 0;   // columns [0, hwm) have been written through the ABI (lazy dot batches never sweep beyond it)
     void touch(int j, int cnt = 1) { if (j + cnt > hwm) hwm = j + cnt; }
     int ed() const { return dtype == LK_C128 ? 2 : 1; }
@@ -280,22 +278,21 @@ struct lk_linop_s {
     OpKind kind;
     int dtype;
     int64_t n;
-    double *dev = nullptr;  // diag values / dense matrix
-    bool own_dev = true;    // dense: the matrix memory belongs to the operator (false: wrapped caller memory)
+    DevBuf<double> dev;     // diag values / dense matrix (owned, or a view of wrapped caller memory)
     int64_t lda = 0;
     // row-sharded dense / CSR: this rank holds rows [rstart[rank], rstart[rank+1]) of an ncols_g x ncols_g operator
     int64_t ncols_g = 0;                  // global size (= n on a single rank)
     std::vector<int64_t> gcounts, gdispls;   // all-gather layout in DOUBLES (per rank)
-    double *xfull = nullptr;              // the gathered input vector / the full-length adjoint product (ncols_g elements)
-    double *gpart = nullptr;              // k_gemv_n's per-chunk partial sums
+    DevBuf<double> xfull;                 // the gathered input vector / the full-length adjoint product (ncols_g elements)
+    DevBuf<double> gpart;                 // k_gemv_n's per-chunk partial sums
     int gchunks = 1;
     // row-sharded CSR, COMPRESSED exchange: only the entries of x that some other rank's rows reference travel.  cx_send_idx =
     // local indices of this rank's entries anybody needs (sorted); every rank's packed entries are all-gathered into cx_xrem
     // (rank r's at cx_displs[r]); the column indices of csr[0] address [own rows | cx_xrem].
     bool cx = false;
-    int32_t *cx_send_idx = nullptr;
+    DevBuf<int32_t> cx_send_idx;
     int64_t cx_nsend = 0, cx_total = 0;
-    double *cx_sendbuf = nullptr, *cx_xrem = nullptr;
+    DevBuf<double> cx_sendbuf, cx_xrem;
     std::vector<int64_t> cx_counts, cx_displs;   // in DOUBLES, per rank
     int64_t row0 = 0;
     double d0 = 0, dstep = 0;
@@ -304,17 +301,18 @@ struct lk_linop_s {
     double gl[8] = {0};   // dx, halfL, nu_re, nu_im, ga_re, ga_im, mu_c, mu2
     double tau = 0;
     int nsub = 1;
-    double *wk = nullptr; // 3 work vectors (k_a, k_b, u_sub)
+    DevBuf<double> wk;    // 3 work vectors (k_a, k_b, u_sub)
     // row-sharded stencil operators
     int64_t NJ = 0;            // lap5: grid lines held by this rank
     int64_t n_global = 0;      // GL: global rows
     bool has_lo = false, has_hi = false;   // a neighbouring rank below / above this block
-    double *halo = nullptr;    // lap5: 2 N doubles (line from rank-1 | line from rank+1); GL: 4 doubles
-    double *edges = nullptr;   // GL: this rank's two edge values (send buffer), 4 doubles
+    DevBuf<double> lap5_halo;  // lap5: 2 N doubles (line from rank-1 | line from rank+1)
+    double *halo = nullptr;    // lap5: lap5_halo; GL: 4 doubles inside wk
+    double *edges = nullptr;   // GL: this rank's two edge values (send buffer), 4 doubles inside wk
     // CSR: A (for 'N') and its conjugate transpose (for 'H'), both row-compressed; W = lanes per row
     struct Csr {
-        int64_t *rowptr = nullptr; int32_t *colind = nullptr; double *vals = nullptr; int W = 8;
-        int64_t *rowblocks = nullptr; int64_t nblocks = 0, nnz_hint = 0;   // CSR-stream partition (short rows), see k_csr_stream
+        DevBuf<int64_t> rowptr; DevBuf<int32_t> colind; DevBuf<double> vals; int W = 8;
+        DevBuf<int64_t> rowblocks; int64_t nblocks = 0, nnz_hint = 0;   // CSR-stream partition (short rows), see k_csr_stream
     } csr[2];
 };
 
@@ -511,7 +509,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             ProfScope ps(c, "dgs_sweep1", bytes, c->prof_ext);
             if (ps.on && ps.ext)
                 hipExtLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, ps.rec.e0, ps.rec.e1, 0, X, ldx, k,
-                                      y, n, c->partial, (int64_t)MAX_GRID, c->guard(), rop);
+                                      y, n, c->partial.get(), (int64_t)MAX_GRID, c->guard(), rop);
             else
                 hipLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, X, ldx, k, y, n, c->partial,
                                    (int64_t)MAX_GRID, c->guard(), rop);
@@ -541,7 +539,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             const int st = (store ? (1 | (c->store_policy << 1) | (c->store_split ? 8 : 0)) : 0) | (c->xcd_map ? 16 : 0);
             if (ps.on && ps.ext)
                 hipExtLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream,
-                                      ps.rec.e0, ps.rec.e1, 0, X, ldx, k, y, n, hin, hin2, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, st,
+                                      ps.rec.e0, ps.rec.e1, 0, X, ldx, k, y, n, hin, hin2, c->partial.get(), (int64_t)MAX_GRID, s.WC, s.kcw, st,
                                       c->guard(), rop);
             else
                 hipLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream, X,
@@ -710,16 +708,6 @@ int block_sweeps(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int pn, const dou
     return LK_OK;
 }
 
-int ensure_scratch(lk_context_t c, int64_t doubles) {
-    if (c->scratch_n >= doubles) return LK_OK;
-    if (c->scratch) HIPCHK(hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_n = 0;
-    HIPCHK(hipMalloc((void **)&c->scratch, (size_t)doubles * sizeof(double)));
-    c->scratch_n = doubles;
-    return LK_OK;
-}
-
 // ---- X^H Y on the matrix cores (panel_xhy_mfma) ---------------------------------------------------------------
 constexpr int XHY_MIN_P = 5;        // fewer right-hand sides: panel_dot_p (<= 4 per pass) reads X once as well
 constexpr int XHY_MAX = 128;        // columns of X and of Y per launch
@@ -762,15 +750,10 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
         //  that an earlier, smaller shape had grown could hold this pass and not the next -- k = 64 then 128 with 17 right-hand sides at n = 4099)
         const int64_t fused = 2 * sect + npart_n + (int64_t)c->num_cu * 2 * nslots;
         if (may_grow && need < fused) need = fused;
-        if (c->xhy_n >= need) return LK_OK;
+        if (c->xhy.capacity() >= need) return LK_OK;
         if (!may_grow)
-            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for a later pass of the block Gram-Schmidt (%lld < %lld)", (long long)c->xhy_n, (long long)need);
-        if (c->xhy) HIPCHK(hipFree(c->xhy));
-        c->xhy = nullptr;
-        c->xhy_n = 0;
-        HIPCHK(hipMalloc((void **)&c->xhy, (size_t)need * sizeof(double)));
-        c->xhy_n = need;
-        return LK_OK;
+            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for a later pass of the block Gram-Schmidt (%lld < %lld)", (long long)c->xhy.capacity(), (long long)need);
+        return c->xhy.reserve(need);
     };
     // complex Gram matrix of 5..112 columns: panel_gram_rs's row split and LDS-DMA tiles with three real products per complex one (panel_gram_rs3m / rs3m4, round 6)
     if (cp && c->gemm_3m && flags == 3 && KP <= 7 && c->gram_rs > 0) {
@@ -913,9 +896,9 @@ int upd_dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, c
     if (g < 1) g = 1;
     const int grid = (int)g;
     const int64_t need = 2 * sect + npart_n + (int64_t)grid * nslots;
-    if (c->xhy_n < need) {
+    if (c->xhy.capacity() < need) {
         // the coefficients of pass A live in this buffer: grow it BEFORE pass A ran (lk_dgs_block sizes it up front), never here
-        return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld < %lld)", (long long)c->xhy_n, (long long)need);
+        return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld < %lld)", (long long)c->xhy.capacity(), (long long)need);
     }
     double *out = c->xhy + (int64_t)slot * XHY_SLOT, *npart = c->xhy + 2 * sect, *part = npart + npart_n;
     // real kind, 17..32 right-hand sides: row-owner waves on LDS-DMA tiles (panel_xhy_upd_rs, round 6): one block of two four-wave teams per CU, two partial blocks per block
@@ -924,8 +907,8 @@ int upd_dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, c
         int64_t gr = c->num_cu;
         if (gr > ntiles) gr = ntiles;
         if (gr < 1) gr = 1;
-        if (c->xhy_n < 2 * sect + npart_n + 2 * gr * nslots)
-            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld)", (long long)c->xhy_n);
+        if (c->xhy.capacity() < 2 * sect + npart_n + 2 * gr * nslots)
+            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld)", (long long)c->xhy.capacity());
         const size_t ldsr = (size_t)4 * (KP * 4096 + 8192);
         {
             ProfScope ps(c, "xhy_upd_mfma", (double)Bx->n * 8.0 * (k + 2 * p));
@@ -1363,7 +1346,7 @@ int fused_sub_with_dots(lk_context_t c) {
     LKCHK((sweepm<2>(q.Bx, q.j0, q.cnt, y, c->coef, nullptr, 1, c->red)));
     LKCHK(fetch(c, 0, 1, red_stride(q.cnt)));
     auto &mm = c->memo;
-    mm.vals.assign(c->red_host, c->red_host + (size_t)q.cnt * ED);
+    mm.vals.assign(c->red_host.get(), c->red_host + (size_t)q.cnt * ED);
     mm.valid = true; mm.xbase = q.Bx->data; mm.y = y; mm.j0 = q.j0; mm.cnt = q.cnt;
     c->nmemo.valid = true; c->nmemo.y = y; c->nmemo.nrm2 = c->red_host[(size_t)q.cnt * ED];
     c->fusion_stats[0] += 1;
@@ -1400,17 +1383,22 @@ constexpr int RES_S = RED_SECTION;                   // slot stride of the hand-
 constexpr int RES_MAX_GRID = RES_GRID_CAP;
 
 int resident_ws(lk_context_t c, ResidentWs *ws) {
+    // each buffer on its own state: one that failed to allocate is tried again by the next launch, the others are not touched
     if (!c->res_cnt) {
-        HIPCHK(hipMalloc((void **)&c->res_cnt, (size_t)RES_CNT_STRIDE * sizeof(unsigned)));
+        LKCHK(c->res_cnt.reserve(RES_CNT_STRIDE));
         HIPCHK(hipMemsetAsync(c->res_cnt, 0, (size_t)RES_CNT_STRIDE * sizeof(unsigned), c->stream));
-        const size_t gran_bytes = (size_t)RES_EPISODES * (RES_GRID_CAP + RES_GROUPS) * RES_S * 16;
-        HIPCHK(hipMalloc(&c->res_gran, gran_bytes));
-        HIPCHK(hipMemsetAsync(c->res_gran, 0, gran_bytes, c->stream));          // (tag 0 is never a launch's)
-        HIPCHK(hipMalloc((void **)&c->res_tim, 8 * sizeof(long long)));
+    }
+    if (!c->res_gran) {
+        const int64_t granules = (int64_t)RES_EPISODES * (RES_GRID_CAP + RES_GROUPS) * RES_S;
+        LKCHK(c->res_gran.reserve(granules));
+        HIPCHK(hipMemsetAsync(c->res_gran, 0, (size_t)granules * sizeof(v2d), c->stream));          // (tag 0 is never a launch's)
+    }
+    if (!c->res_tim) {
+        LKCHK(c->res_tim.reserve(8));
         HIPCHK(hipMemsetAsync(c->res_tim, 0, 8 * sizeof(long long), c->stream));
     }
     ws->tim = c->res_tim;
-    ws->gran = (v2d *)c->res_gran;
+    ws->gran = c->res_gran;
     ws->epoch = ++c->res_epoch;
     ws->cnt = c->res_cnt;
     ws->S = RES_S;
@@ -1569,17 +1557,17 @@ int lk_init(int device, void *stream, lk_context_t *ctx) {
             HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
             c->own_stream = true;
         }
-        HIPCHK(hipMalloc((void **)&c->partial, (size_t)PARTIAL_SECTIONS * RED_SECTION * MAX_GRID * sizeof(double)));
+        LKCHK(c->partial.reserve((int64_t)PARTIAL_SECTIONS * RED_SECTION * MAX_GRID));
         // sized for the wide layouts too: 9 sections of RED_SECTION_WIDE (the narrow layouts use the head of the same buffer)
-        HIPCHK(hipMalloc((void **)&c->red, (size_t)RED_TOTAL * RED_SECTION_WIDE * sizeof(double)));
+        LKCHK(c->red.reserve((int64_t)RED_TOTAL * RED_SECTION_WIDE));
         HIPCHK(hipMemsetAsync(c->red, 0, (size_t)RED_TOTAL * RED_SECTION_WIDE * sizeof(double), c->stream));
-        HIPCHK(hipHostMalloc((void **)&c->red_host, (size_t)RED_TOTAL * RED_SECTION_WIDE * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&c->coef, (size_t)KMAX_WIDE * 2 * sizeof(double)));
-        HIPCHK(hipHostMalloc((void **)&c->coef_host, (size_t)KMAX_WIDE * 2 * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&c->stop_dev, sizeof(int)));
+        LKCHK(c->red_host.reserve((int64_t)RED_TOTAL * RED_SECTION_WIDE));
+        LKCHK(c->coef.reserve(KMAX_WIDE * 2));
+        LKCHK(c->coef_host.reserve(KMAX_WIDE * 2));
+        LKCHK(c->stop_dev.reserve(1));
         HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
-        HIPCHK(hipHostMalloc((void **)&c->stop_host, sizeof(int), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void **)&c->expm_host, 2 * sizeof(double), hipHostMallocDefault));
+        LKCHK(c->stop_host.reserve(1));
+        LKCHK(c->expm_host.reserve(2));
         HIPCHK(hipEventCreateWithFlags(&c->coef_ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->coef_ev, c->stream));
         return LK_OK;
@@ -1628,31 +1616,12 @@ int lk_finalize(lk_context_t c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     prof_collect(c);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->partial) (void)hipFree(c->partial);
-    if (c->red) (void)hipFree(c->red);
-    if (c->coef) (void)hipFree(c->coef);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->xhy) (void)hipFree(c->xhy);
-    if (c->lz_red) (void)hipFree(c->lz_red);
-    if (c->lz_red_host) (void)hipHostFree(c->lz_red_host);
-    if (c->red_host) (void)hipHostFree(c->red_host);
-    if (c->coef_host) (void)hipHostFree(c->coef_host);
     if (c->coef_ev) (void)hipEventDestroy(c->coef_ev);
-    if (c->stop_dev) (void)hipFree(c->stop_dev);
-    if (c->stop_host) (void)hipHostFree(c->stop_host);
-    if (c->expm_host) (void)hipHostFree(c->expm_host);
-    if (c->seg_stop_host) (void)hipHostFree(c->seg_stop_host);
     for (auto e : c->seg_events) (void)hipEventDestroy(e);
-    c->seg_events.clear();
-    if (c->step_red) (void)hipFree(c->step_red);
-    if (c->step_red_host) (void)hipHostFree(c->step_red_host);
-    if (c->res_cnt) (void)hipFree(c->res_cnt);
-    if (c->res_tim) (void)hipFree(c->res_tim);
-    if (c->blk_red) (void)hipFree(c->blk_red);
-    if (c->blk_red_host) (void)hipHostFree(c->blk_red_host);
-    if (c->res_gran) (void)hipFree(c->res_gran);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    // the workspaces go with the context: here, on its device and behind the synchronisation above, and before a stream of its own does
+    const hipStream_t owned = c->own_stream ? c->stream : nullptr;
     delete c;
+    if (owned) (void)hipStreamDestroy(owned);
     return LK_OK;
 }
 
@@ -1829,18 +1798,11 @@ int lk_basis_create(lk_context_t c, int dtype, int64_t n_local, int ncols, lk_ba
     const int64_t align_elems = 256 / (8 * ed);  // 256-byte column alignment
     int64_t ld = ((n_local + align_elems - 1) / align_elems) * align_elems;
     if (ld == 0) ld = align_elems;
-    lk_basis_t b = new lk_basis_s();
-    b->ctx = c; b->dtype = dtype; b->n = n_local; b->ld = ld; b->ncols = ncols; b->own = true; b->data = nullptr;
-    const size_t bytes = (size_t)ld * ncols * ed * sizeof(double);
-    hipError_t e = hipMalloc((void **)&b->data, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();      // clear the runtime's sticky last-error state: the NEXT launch check must not report this
-        delete b;
-        return fail(LK_ERR_NOMEM, "lk_basis_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    e = hipMemsetAsync(b->data, 0, bytes, c->stream);
-    if (e != hipSuccess) { (void)hipFree(b->data); delete b; return fail(LK_ERR_HIP, "memset failed: %s", hipGetErrorString(e)); }
-    *B = b;
+    std::unique_ptr<lk_basis_s> b(new lk_basis_s());
+    b->ctx = c; b->dtype = dtype; b->n = n_local; b->ld = ld; b->ncols = ncols;
+    LKCHK(b->data.reserve(ld * ncols * ed));
+    HIPCHK(hipMemsetAsync(b->data, 0, (size_t)ld * ncols * ed * sizeof(double), c->stream));
+    *B = b.release();
     return LK_OK;
 }
 
@@ -1851,7 +1813,7 @@ int lk_basis_wrap(lk_context_t c, int dtype, int64_t n_local, int ncols, int64_t
     if (((uintptr_t)dev_ptr & 15) != 0) return fail(LK_ERR_INVALID, "lk_basis_wrap: pointer must be 16-byte aligned");
     if (dtype == LK_F64 && (ld & 1) && ncols > 1) return fail(LK_ERR_INVALID, "lk_basis_wrap: ld must be even for LK_F64");
     lk_basis_t b = new lk_basis_s();
-    b->ctx = c; b->dtype = dtype; b->n = n_local; b->ld = ld; b->ncols = ncols; b->own = false; b->data = (double *)dev_ptr;
+    b->ctx = c; b->dtype = dtype; b->n = n_local; b->ld = ld; b->ncols = ncols; b->data.wrap((double *)dev_ptr);
     b->hwm = ncols;   // caller-owned memory: every column may hold data
     *B = b;
     return LK_OK;
@@ -1866,14 +1828,13 @@ int lk_basis_destroy(lk_basis_t B) {
             DevGuard dev_guard(c);               // the flush below launches on c->stream: run it on the context's device
             auto &q = c->queue;
             // (a non-owning handle is a VIEW of memory that lives on: what is pending there must be written)
-            const bool only_target = B->own && q.active && q.zeroed && q.By == B && q.Bx != B && !(c->sub.active && c->sub.By == B);
+            const bool only_target = B->data.owns() && q.active && q.zeroed && q.By == B && q.Bx != B && !(c->sub.active && c->sub.By == B);
             if (only_target) q.By = nullptr;     // a virtual temporary dies unwritten; its coefficients may still serve `sub`
             else (void)lazy_flush(c);
             c->forget_memos();
         }
     }
-    // hipFree waits for outstanding device work itself; the context may already be finalized.
-    if (B->own && B->data) (void)hipFree(B->data);
+    // (the release of an owned panel waits for outstanding device work itself; the context may already be finalized)
     delete B;
     return LK_OK;
 }
@@ -2184,7 +2145,7 @@ static int speculative_first_pass(lk_context_t c, lk_basis_t B, int j, int *done
     LKCHK((sweepm<1>(B, sp.j0, cnt, y, nullptr, nullptr, 0, c->red)));
     LKCHK(fetch(c, 0, 1, red_stride(cnt)));
     auto &mm = c->memo;
-    mm.vals.assign(c->red_host, c->red_host + (size_t)cnt * ED);
+    mm.vals.assign(c->red_host.get(), c->red_host + (size_t)cnt * ED);
     mm.valid = true; mm.xbase = B->data; mm.y = y; mm.j0 = sp.j0; mm.cnt = cnt;
     c->nmemo.valid = true; c->nmemo.y = y; c->nmemo.nrm2 = c->red_host[(size_t)cnt * ED];
     sp.jy = j; sp.unused = true;
@@ -2283,7 +2244,7 @@ int lk_vec_dot(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out) {
         if (cnt >= 2 && !y_inside) {
             LKCHK((sweepm<1>(Bx, jx, cnt, By->col(jy), nullptr, nullptr, 0, c->red)));
             LKCHK(fetch(c, 0, 1, red_stride(cnt)));
-            mm.vals.assign(c->red_host, c->red_host + (size_t)cnt * ED);
+            mm.vals.assign(c->red_host.get(), c->red_host + (size_t)cnt * ED);
             mm.valid = true; mm.xbase = Bx->data; mm.y = yp; mm.j0 = jx; mm.cnt = cnt;
             c->lazy_stats[1] += 1;
             // norm of column jy, then the dots of ALL columns before it against it: the opening of a Gram-Schmidt pass against
@@ -2477,7 +2438,7 @@ int lk_lincomb(lk_basis_t Bx, int k, const double *C, int q, lk_basis_t By, int 
     if (Bx->data == By->data && jy0 < k) return fail(LK_ERR_INVALID, "lk_lincomb: output columns alias the input basis");
     // coefficients: one upload of the whole k x q block, repacked on the device for the kernel's scalar loads
     const int64_t raw = (int64_t)k * q * ED;
-    LKCHK(ensure_scratch(c, raw + gemm_packed_doubles(k, q, ED)));
+    LKCHK(c->scratch.reserve(raw + gemm_packed_doubles(k, q, ED)));
     HIPCHK(hipMemcpyAsync(c->scratch, C, (size_t)raw * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LKCHK(gemm_launch(Bx, 0, k, By, jy0, q, c->scratch, (int64_t)k, 1.0, 0, c->scratch + raw));
     HIPCHK(hipStreamSynchronize(c->stream));   // the host coefficient array may be released by the caller
@@ -2628,7 +2589,7 @@ int lk_dgs(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *h, double *norms
 // Y(:, jy0:jy0+qn) -= X(:, :k) * C, C = device coefficients laid out [q][ldc][ED] (what the multi-RHS dot sweep leaves in c->red)
 static int gemm_subtract(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int qn, const double *Cdev, int64_t ldc, int c0 = 0) {
     lk_context_t c = Bx->ctx;
-    LKCHK(ensure_scratch(c, gemm_packed_doubles(k, qn, Bx->ed())));
+    LKCHK(c->scratch.reserve(gemm_packed_doubles(k, qn, Bx->ed())));
     return gemm_launch(Bx, c0, k, By, jy0, qn, Cdev, ldc, -1.0, 1, c->scratch);
 }
 
@@ -2769,14 +2730,8 @@ static int dgs_block_walk(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, d
 }
 
 static int ensure_block_buffers(lk_context_t c, int64_t doubles) {
-    if (c->blk_cap >= doubles) return LK_OK;
-    if (c->blk_red) HIPCHK(hipFree(c->blk_red));
-    if (c->blk_red_host) HIPCHK(hipHostFree(c->blk_red_host));
-    c->blk_red = nullptr; c->blk_red_host = nullptr; c->blk_cap = 0;
-    HIPCHK(hipMalloc((void **)&c->blk_red, (size_t)doubles * sizeof(double)));
-    HIPCHK(hipHostMalloc((void **)&c->blk_red_host, (size_t)doubles * sizeof(double), hipHostMallocDefault));
-    c->blk_cap = doubles;
-    return LK_OK;
+    LKCHK(c->blk_red.reserve(doubles));
+    return c->blk_red_host.reserve(doubles);
 }
 
 int lk_dgs_block(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, double *h, int *info) {
@@ -2811,14 +2766,12 @@ int lk_linop_diag_create(lk_context_t c, int dtype, int64_t n_local, const void 
     if (!c || !d_host || !op) return fail(LK_ERR_INVALID, "lk_linop_diag_create: null argument");
     DevGuard dev_guard(c);
     if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "bad dtype");
-    lk_linop_t o = new lk_linop_s();
+    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
     o->ctx = c; o->kind = OP_DIAG; o->dtype = dtype; o->n = n_local;
-    const size_t bytes = (size_t)(n_local + 2) * (dtype == LK_C128 ? 2 : 1) * sizeof(double);
-    hipError_t e = hipMalloc((void **)&o->dev, bytes);
-    if (e != hipSuccess) { delete o; return fail(LK_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e)); }
-    e = hipMemcpy(o->dev, d_host, (size_t)n_local * (dtype == LK_C128 ? 2 : 1) * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(o->dev); delete o; return fail(LK_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e)); }
-    *op = o;
+    const int ED = dtype == LK_C128 ? 2 : 1;
+    LKCHK(o->dev.reserve((n_local + 2) * ED));
+    HIPCHK(hipMemcpy(o->dev, d_host, (size_t)n_local * ED * sizeof(double), hipMemcpyHostToDevice));
+    *op = o.release();
     return LK_OK;
 }
 
@@ -2846,7 +2799,7 @@ static int shard_setup(lk_linop_t o, lk_context_t c, int64_t n_global, const int
         o->gcounts[r] = (row_starts[r + 1] - row_starts[r]) * ED;
         o->gdispls[r] = row_starts[r] * ED;
     }
-    if (c->nranks > 1) HIPCHK(hipMalloc((void **)&o->xfull, (size_t)(n_global > 0 ? n_global : 1) * ED * sizeof(double)));
+    if (c->nranks > 1) LKCHK(o->xfull.reserve((n_global > 0 ? n_global : 1) * ED));
     return LK_OK;
 }
 
@@ -2860,7 +2813,19 @@ static int dense_finish(lk_linop_t o, lk_context_t c) {
     if (chunks < 1) chunks = 1;
     o->gchunks = (int)chunks;
     const int ED = o->dtype == LK_C128 ? 2 : 1;
-    HIPCHK(hipMalloc((void **)&o->gpart, (size_t)chunks * (o->n > 0 ? o->n : 1) * ED * sizeof(double)));
+    return o->gpart.reserve(chunks * (o->n > 0 ? o->n : 1) * ED);
+}
+
+// the row-sharded dense operator on `A`: the operator's own matrix, or a view of caller memory
+static int dense_build(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, DevBuf<double> A, int64_t lda, lk_linop_t *op) {
+    if (((uintptr_t)(double *)A & 15) != 0) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: pointer must be 16-byte aligned");
+    if (dtype == LK_F64 && (lda & 1)) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda must be even for LK_F64");
+    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
+    o->ctx = c; o->kind = OP_DENSE; o->dtype = dtype; o->dev = std::move(A); o->lda = lda;
+    LKCHK(shard_setup(o.get(), c, n_global, row_starts, "lk_linop_dense_wrap_sharded"));
+    if (lda < o->n) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda < local rows");
+    LKCHK(dense_finish(o.get(), c));
+    *op = o.release();
     return LK_OK;
 }
 
@@ -2869,16 +2834,9 @@ int lk_linop_dense_wrap_sharded(lk_context_t c, int dtype, int64_t n_global, con
     if (!c || !dev_ptr || !op) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: null argument");
     DevGuard dev_guard(c);
     if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "bad dtype");
-    if (((uintptr_t)dev_ptr & 15) != 0) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: pointer must be 16-byte aligned");
-    if (dtype == LK_F64 && (lda & 1)) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda must be even for LK_F64");
-    lk_linop_t o = new lk_linop_s();
-    o->ctx = c; o->kind = OP_DENSE; o->dtype = dtype; o->dev = (double *)dev_ptr; o->own_dev = false; o->lda = lda;
-    int rc = shard_setup(o, c, n_global, row_starts, "lk_linop_dense_wrap_sharded");
-    if (rc == LK_OK && lda < o->n) rc = fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda < local rows");
-    if (rc == LK_OK) rc = dense_finish(o, c);
-    if (rc != LK_OK) { (void)lk_linop_destroy(o); return rc; }
-    *op = o;
-    return LK_OK;
+    DevBuf<double> A;
+    A.wrap((double *)dev_ptr);
+    return dense_build(c, dtype, n_global, row_starts, std::move(A), lda, op);
 }
 
 int lk_linop_dense_create_sharded(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, const void *A_rows, int64_t lda,
@@ -2890,17 +2848,11 @@ int lk_linop_dense_create_sharded(lk_context_t c, int dtype, int64_t n_global, c
     if (n_local < 0 || lda < n_local) return fail(LK_ERR_INVALID, "lk_linop_dense_create_sharded: lda < local rows");
     const size_t es = (dtype == LK_C128 ? 2 : 1) * sizeof(double);
     const int64_t ldd = ((n_local + 31) / 32) * 32 + (n_local == 0 ? 32 : 0);          // 256-byte columns on the device
-    double *dev = nullptr;
-    hipError_t e = hipMalloc((void **)&dev, (size_t)ldd * (n_global > 0 ? n_global : 1) * es);
-    if (e != hipSuccess) return fail(LK_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    if (n_local > 0 && n_global > 0) {
-        e = hipMemcpy2D(dev, (size_t)ldd * es, A_rows, (size_t)lda * es, (size_t)n_local * es, n_global, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(dev); return fail(LK_ERR_HIP, "hipMemcpy2D failed: %s", hipGetErrorString(e)); }
-    }
-    const int rc = lk_linop_dense_wrap_sharded(c, dtype, n_global, row_starts, dev, ldd, op);
-    if (rc != LK_OK) { (void)hipFree(dev); return rc; }
-    (*op)->own_dev = true;
-    return LK_OK;
+    DevBuf<double> dev;
+    LKCHK(dev.reserve(ldd * (n_global > 0 ? n_global : 1) * (dtype == LK_C128 ? 2 : 1)));
+    if (n_local > 0 && n_global > 0)
+        HIPCHK(hipMemcpy2D(dev, (size_t)ldd * es, A_rows, (size_t)lda * es, (size_t)n_local * es, n_global, hipMemcpyHostToDevice));
+    return dense_build(c, dtype, n_global, row_starts, std::move(dev), ldd, op);
 }
 
 int lk_linop_dense_create(lk_context_t c, int dtype, int64_t n, const void *A_host, int64_t lda, lk_linop_t *op) {
@@ -2959,21 +2911,20 @@ int lk_set_halo_exchange(lk_context_t c, lk_halo_fn fn, void *user) {
 int lk_linop_lap5_create_sharded(lk_context_t c, int64_t N, int64_t j0, int64_t nj, lk_linop_t *op) {
     if (!c || !op || N < 1 || j0 < 0 || nj < 1 || j0 + nj > N) return fail(LK_ERR_INVALID, "lk_linop_lap5_create: bad argument");
     DevGuard dev_guard(c);
-    lk_linop_t o = new lk_linop_s();
+    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
     o->ctx = c; o->kind = OP_LAP5; o->dtype = LK_F64; o->n = nj * N; o->N = N; o->NJ = nj;
     o->has_lo = j0 > 0; o->has_hi = j0 + nj < N;
     // the halo exchange addresses its peers by RANK ORDER (rank - 1 below, rank + 1 above): a partition that does not follow
     // it would skip a send on one side and leave the neighbour waiting
     if (c->nranks > 1 && (o->has_lo != (c->rank > 0) || o->has_hi != (c->rank < c->nranks - 1))) {
-        delete o;
         return fail(LK_ERR_INVALID, "lk_linop_lap5_create_sharded: grid lines [%lld, %lld) of %lld on rank %d/%d do not follow rank order "
                     "(rank r must own the r-th consecutive block)", (long long)j0, (long long)(j0 + nj), (long long)N, c->rank, c->nranks);
     }
     if (o->has_lo || o->has_hi) {
-        hipError_t e = hipMalloc((void **)&o->halo, (size_t)2 * N * sizeof(double));
-        if (e != hipSuccess) { delete o; return fail(LK_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e)); }
+        LKCHK(o->lap5_halo.reserve(2 * N));
+        o->halo = o->lap5_halo;
     }
-    *op = o;
+    *op = o.release();
     return LK_OK;
 }
 
@@ -2987,23 +2938,21 @@ int lk_linop_gl_create_sharded(lk_context_t c, int64_t n_global, int64_t row0, i
     if (!c || !op || !nu || !gamma || n_global < 1 || n_local < 1 || row0 < 0 || row0 + n_local > n_global || nsub < 1 || !(dx > 0.0))
         return fail(LK_ERR_INVALID, "lk_linop_gl_create: bad argument");
     DevGuard dev_guard(c);
-    lk_linop_t o = new lk_linop_s();
+    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
     o->ctx = c; o->kind = OP_GL; o->dtype = LK_C128; o->n = n_local; o->tau = tau; o->nsub = nsub;
     o->row0 = row0; o->n_global = n_global;
     o->has_lo = row0 > 0; o->has_hi = row0 + n_local < n_global;
     if (c->nranks > 1 && (o->has_lo != (c->rank > 0) || o->has_hi != (c->rank < c->nranks - 1))) {
-        delete o;
         return fail(LK_ERR_INVALID, "lk_linop_gl_create_sharded: rows [%lld, %lld) of %lld on rank %d/%d do not follow rank order "
                     "(rank r must own the r-th consecutive block)", (long long)row0, (long long)(row0 + n_local), (long long)n_global, c->rank, c->nranks);
     }
     o->gl[0] = dx; o->gl[1] = 0.5 * dx * (double)(n_global + 1);   // L = dx (n+1), x = linspace(-L/2, L/2, n+2)
     o->gl[2] = nu[0]; o->gl[3] = nu[1]; o->gl[4] = gamma[0]; o->gl[5] = gamma[1]; o->gl[6] = mu_c; o->gl[7] = mu2;
-    hipError_t e = hipMalloc((void **)&o->wk, ((size_t)3 * n_local * 2 + 8) * sizeof(double));
-    if (e != hipSuccess) { delete o; return fail(LK_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e)); }
+    LKCHK(o->wk.reserve(3 * n_local * 2 + 8));
     o->halo = o->wk + (size_t)6 * n_local;      // 4 doubles
     o->edges = o->halo + 4;                     // 4 doubles
     (void)hipMemsetAsync(o->halo, 0, 8 * sizeof(double), c->stream);
-    *op = o;
+    *op = o.release();
     return LK_OK;
 }
 
@@ -3018,9 +2967,9 @@ int lk_linop_gl_create(lk_context_t c, int64_t n, double dx, double tau, int nsu
 static int csr_upload(lk_linop_t o, int which, int64_t n, const int64_t *rowptr, const int32_t *colind, const double *vals, int ED) {
     const int64_t nnz = rowptr[n];
     auto &m = o->csr[which];
-    HIPCHK(hipMalloc((void **)&m.rowptr, (size_t)(n + 1) * sizeof(int64_t)));
-    HIPCHK(hipMalloc((void **)&m.colind, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&m.vals, (size_t)(nnz > 0 ? nnz : 1) * ED * sizeof(double)));
+    LKCHK(m.rowptr.reserve(n + 1));
+    LKCHK(m.colind.reserve(nnz > 0 ? nnz : 1));
+    LKCHK(m.vals.reserve((nnz > 0 ? nnz : 1) * ED));
     HIPCHK(hipMemcpy(m.rowptr, rowptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz > 0) {
         HIPCHK(hipMemcpy(m.colind, colind, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -3037,7 +2986,7 @@ static int csr_upload(lk_linop_t o, int which, int64_t n, const int64_t *rowptr,
             r = e;
         }
         m.nblocks = (int64_t)rb.size() - 1;
-        HIPCHK(hipMalloc((void **)&m.rowblocks, rb.size() * sizeof(int64_t)));
+        LKCHK(m.rowblocks.reserve((int64_t)rb.size()));
         HIPCHK(hipMemcpy(m.rowblocks, rb.data(), rb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     m.nnz_hint = nnz;
@@ -3056,17 +3005,15 @@ static int host_allgatherv(lk_context_t c, const std::vector<double> &mine, cons
     all.assign((size_t)total, 0.0);
     if (total == 0) return LK_OK;
     if (!c->allgather) return fail(LK_ERR_COMM, "row-sharded CSR operator but no all-gather installed (lk_comm_init_rank / lk_set_allgather)");
-    double *ds = nullptr, *dr = nullptr;
-    HIPCHK(hipMalloc((void **)&ds, (size_t)(mine.size() > 0 ? mine.size() : 1) * sizeof(double)));
-    hipError_t e = hipMalloc((void **)&dr, (size_t)total * sizeof(double));
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(ds); return fail(LK_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e)); }
+    DevBuf<double> ds, dr;
+    LKCHK(ds.reserve(mine.size() > 0 ? (int64_t)mine.size() : 1));
+    LKCHK(dr.reserve(total));
     int rc = LK_OK;
     if (!mine.empty() && hipMemcpyAsync(ds, mine.data(), mine.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "metadata upload failed");
     if (rc == LK_OK && c->allgather(c->allgather_user, ds, dr, counts.data(), displs.data(), c->nranks, (void *)c->stream) != 0)
         rc = fail(LK_ERR_COMM, "all-gather callback failed (metadata)");
     if (rc == LK_OK && hipMemcpyAsync(all.data(), dr, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "metadata download failed");
     if (rc == LK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "stream synchronisation failed");
-    (void)hipFree(ds); (void)hipFree(dr);
     return rc;
 }
 
@@ -3170,11 +3117,10 @@ static int csr_compress_setup(lk_linop_t o, lk_context_t c, const int64_t *row_s
     o->cx_nsend = (int64_t)S[me].size();
     std::vector<int32_t> sidx((size_t)(o->cx_nsend > 0 ? o->cx_nsend : 1), 0);
     for (int64_t i = 0; i < o->cx_nsend; ++i) sidx[(size_t)i] = (int32_t)(S[me][(size_t)i] - row0);
-    HIPCHK(hipMalloc((void **)&o->cx_send_idx, sidx.size() * sizeof(int32_t)));
+    LKCHK(o->cx_send_idx.reserve((int64_t)sidx.size()));
     HIPCHK(hipMemcpy(o->cx_send_idx, sidx.data(), sidx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&o->cx_sendbuf, (size_t)(o->cx_nsend > 0 ? o->cx_nsend : 1) * ED * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&o->cx_xrem, (size_t)(total > 0 ? total : 1) * ED * sizeof(double)));
-    return LK_OK;
+    LKCHK(o->cx_sendbuf.reserve((o->cx_nsend > 0 ? o->cx_nsend : 1) * ED));
+    return o->cx_xrem.reserve((total > 0 ? total : 1) * ED);
 }
 
 // local (rank-private) validation of a row block: nothing here talks to another rank
@@ -3215,7 +3161,7 @@ int lk_linop_csr_create_sharded(lk_context_t c, int dtype, int64_t n_global, con
     std::vector<int64_t> tp;
     std::vector<int32_t> tc;
     std::vector<double> tv;
-    lk_linop_t o = nullptr;
+    std::unique_ptr<lk_linop_s> o;
     int rc_host = LK_OK;
     try {
         tp.assign((size_t)n_global + 1, 0);
@@ -3231,29 +3177,29 @@ int lk_linop_csr_create_sharded(lk_context_t c, int dtype, int64_t n_global, con
                 tv[(size_t)q * ED] = v[p * ED];
                 if (ED == 2) tv[(size_t)q * 2 + 1] = -v[p * 2 + 1];
             }
-        o = new lk_linop_s();
+        o.reset(new lk_linop_s());
         o->ctx = c; o->kind = OP_CSR; o->dtype = dtype;
     } catch (const std::exception &e) {
         rc_host = fail(LK_ERR_NOMEM, "lk_linop_csr_create_sharded: host allocation failed while transposing this rank's rows (%s)", e.what());
     }
     // ... then this rank's share of the set-up that precedes the metadata exchange (the transpose above, the gathered-x buffer) ...
-    int rc = agree_status(c, rc_host != LK_OK ? rc_host : shard_setup(o, c, n_global, row_starts, "lk_linop_csr_create"), "lk_linop_csr_create_sharded (buffers)");
+    int rc = agree_status(c, rc_host != LK_OK ? rc_host : shard_setup(o.get(), c, n_global, row_starts, "lk_linop_csr_create"), "lk_linop_csr_create_sharded (buffers)");
     if (rc == LK_OK) {
         // ... the metadata exchange itself (its decisions come from quantities every rank holds identically; its staging buffers
         // are a few P-length tables and the request lists -- a rank that cannot allocate THOSE is fatal for the job, see header) ...
         try {
             std::vector<int32_t> cols0;
-            rc = csr_compress_setup(o, c, row_starts, n, rowptr, colind, cols0);
-            if (rc == LK_OK) rc = csr_upload(o, 0, n, rowptr, cols0.data(), v, ED);
-            if (rc == LK_OK) rc = csr_upload(o, 1, n_global, tp.data(), tc.data(), tv.data(), ED);
+            rc = csr_compress_setup(o.get(), c, row_starts, n, rowptr, colind, cols0);
+            if (rc == LK_OK) rc = csr_upload(o.get(), 0, n, rowptr, cols0.data(), v, ED);
+            if (rc == LK_OK) rc = csr_upload(o.get(), 1, n_global, tp.data(), tc.data(), tv.data(), ED);
         } catch (const std::exception &e) {
             rc = fail(LK_ERR_NOMEM, "lk_linop_csr_create_sharded: host allocation failed (%s)", e.what());
         }
         // ... and finally the uploads: an operator exists on every rank or on none
         rc = agree_status(c, rc, "lk_linop_csr_create_sharded (upload)");
     }
-    if (rc != LK_OK) { if (o) (void)lk_linop_destroy(o); return rc; }
-    *op = o;
+    if (rc != LK_OK) return rc;
+    *op = o.release();
     return LK_OK;
 }
 
@@ -3266,22 +3212,7 @@ int lk_linop_csr_create(lk_context_t c, int dtype, int64_t n, const int64_t *row
 }
 
 int lk_linop_destroy(lk_linop_t op) {
-    if (!op) return LK_OK;
-    for (auto &m : op->csr) {
-        if (m.rowptr) (void)hipFree(m.rowptr);
-        if (m.colind) (void)hipFree(m.colind);
-        if (m.vals) (void)hipFree(m.vals);
-        if (m.rowblocks) (void)hipFree(m.rowblocks);
-    }
-    if (op->kind == OP_LAP5 && op->halo) (void)hipFree(op->halo);
-    if (op->wk) (void)hipFree(op->wk);
-    if (op->xfull) (void)hipFree(op->xfull);
-    if (op->cx_send_idx) (void)hipFree(op->cx_send_idx);
-    if (op->cx_sendbuf) (void)hipFree(op->cx_sendbuf);
-    if (op->cx_xrem) (void)hipFree(op->cx_xrem);
-    if (op->gpart) (void)hipFree(op->gpart);
-    if (op->dev && op->own_dev) (void)hipFree(op->dev);  // synchronises; the context may already be finalized
-    delete op;
+    delete op;   // what the operator owns goes with it (the frees synchronise); op->ctx may already be finalized and is not touched
     return LK_OK;
 }
 
@@ -3350,7 +3281,8 @@ int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t B
         break;
     }
     case OP_CSR: {
-        auto m = op->csr[trans == LK_OP_N ? 0 : 1];
+        const auto &m = op->csr[trans == LK_OP_N ? 0 : 1];
+        const int W = c->csr_lanes ? c->csr_lanes : m.W;                 // (a forced lane count is never written into the operator)
         // row-sharded: 'N' multiplies this rank's rows with the all-gathered x; 'H' applies the conjugate transpose of the row
         // block (n_global rows) to this rank's x, sums the full-length results over the ranks and keeps this rank's rows
         const bool shard = c->nranks > 1;
@@ -3390,8 +3322,7 @@ int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t B
             launched = true;
         }
         if (!launched) {
-            if (c->csr_lanes) m.W = c->csr_lanes;
-            const int64_t rows_per_block = 256 / m.W;
+            const int64_t rows_per_block = 256 / W;
             int64_t g = (nr + rows_per_block - 1) / rows_per_block;
             const int64_t cap = (int64_t)c->num_cu * 16;
             if (g > cap) g = cap;
@@ -3401,9 +3332,9 @@ int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t B
         if (cp) hipLaunchKernelGGL((k_csr<true, WW>), dim3((unsigned)g), dim3(256), 0, c->stream, m.rowptr, m.colind, m.vals, xin, yout, nr, c->guard(), xrem, nloc); \
         else hipLaunchKernelGGL((k_csr<false, WW>), dim3((unsigned)g), dim3(256), 0, c->stream, m.rowptr, m.colind, m.vals, xin, yout, nr, c->guard(), xrem, nloc);   \
         break;
-            switch (m.W) {
+            switch (W) {
                 LK_CSR_LAUNCH(1) LK_CSR_LAUNCH(2) LK_CSR_LAUNCH(4) LK_CSR_LAUNCH(8) LK_CSR_LAUNCH(16) LK_CSR_LAUNCH(32) LK_CSR_LAUNCH(64)
-            default: return fail(LK_ERR_INVALID, "internal: CSR lanes per row %d", m.W);
+            default: return fail(LK_ERR_INVALID, "internal: CSR lanes per row %d", W);
             }
 #undef LK_CSR_LAUNCH
         }
@@ -3499,15 +3430,8 @@ static int arnoldi_step_sync(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh,
 // per-step result slots of an asynchronous batch: nsteps x RED_SECTIONS sections of `stride` doubles (red_stride(last step))
 static int ensure_step_buffers(lk_context_t c, int nsteps, int stride) {
     const int64_t need = (int64_t)nsteps * RED_SECTIONS * stride;
-    if (c->step_red_cap >= need) return LK_OK;
-    if (c->step_red) HIPCHK(hipFree(c->step_red));
-    if (c->step_red_host) HIPCHK(hipHostFree(c->step_red_host));
-    c->step_red = nullptr; c->step_red_host = nullptr; c->step_red_cap = 0;
-    const size_t bytes = (size_t)need * sizeof(double);
-    HIPCHK(hipMalloc((void **)&c->step_red, bytes));
-    HIPCHK(hipHostMalloc((void **)&c->step_red_host, bytes, hipHostMallocDefault));
-    c->step_red_cap = need;
-    return LK_OK;
+    LKCHK(c->step_red.reserve(need));
+    return c->step_red_host.reserve(need);
 }
 
 // Steps [k0, k1] (all <= KMAX_WIDE) enqueued back to back with NO host round trip: operator, three fused sweeps and
@@ -3546,16 +3470,11 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
     const int nsteps = k1 - k0 + 1;
     const int rs = red_stride(k1);                  // one section size for every step of the batch
     LKCHK(ensure_step_buffers(c, nsteps, rs));
-    if (nseg > c->seg_cap) {
-        if (c->seg_stop_host) HIPCHK(hipHostFree(c->seg_stop_host));
-        c->seg_stop_host = nullptr;
-        HIPCHK(hipHostMalloc((void **)&c->seg_stop_host, (size_t)nseg * sizeof(int), hipHostMallocDefault));
-        while ((int)c->seg_events.size() < nseg) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->seg_events.push_back(e);
-        }
-        c->seg_cap = nseg;
+    LKCHK(c->seg_stop_host.reserve(nseg));
+    while ((int)c->seg_events.size() < nseg) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->seg_events.push_back(e);
     }
     HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;
@@ -3657,15 +3576,8 @@ static int lanczos_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
     const int nsteps = k1 - k0 + 1;
     const int rs = red_stride(k1);
     LKCHK(ensure_step_buffers(c, nsteps, rs));
-    if (c->lz_cap < nsteps) {
-        if (c->lz_red) HIPCHK(hipFree(c->lz_red));
-        if (c->lz_red_host) HIPCHK(hipHostFree(c->lz_red_host));
-        c->lz_red = nullptr; c->lz_red_host = nullptr; c->lz_cap = 0;
-        const size_t bytes = (size_t)nsteps * 4 * RED_SECTION * sizeof(double);
-        HIPCHK(hipMalloc((void **)&c->lz_red, bytes));
-        HIPCHK(hipHostMalloc((void **)&c->lz_red_host, bytes, hipHostMallocDefault));
-        c->lz_cap = nsteps;
-    }
+    LKCHK(c->lz_red.reserve((int64_t)nsteps * 4 * RED_SECTION));
+    LKCHK(c->lz_red_host.reserve((int64_t)nsteps * 4 * RED_SECTION));
     HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;     // below it: stop flag AND no scaling (lanczos.fypp:32-36)
     c->guard_on = true;
@@ -4010,11 +3922,9 @@ static int arnoldi_impl(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int 
 // ---- qr_no_pivoting and the block Arnoldi factorisation ---------------------------------------------------------------------------
 // a view of columns [c0, c0 + ncols) of a panel (not owned): the basis Q(:j-1) a column of the block is orthogonalised against
 static lk_basis_s basis_view(lk_basis_t B, int c0, int ncols) {
-    lk_basis_s v = *B;
-    v.data = B->col(c0);
-    v.ncols = ncols;
-    v.own = false;
-    v.hwm = ncols;
+    lk_basis_s v;
+    v.ctx = B->ctx; v.dtype = B->dtype; v.n = B->n; v.ld = B->ld; v.ncols = ncols; v.hwm = ncols;
+    v.data.wrap(B->col(c0));
     return v;
 }
 
