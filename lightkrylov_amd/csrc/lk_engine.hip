@@ -272,50 +272,6 @@ struct lk_basis_s {
     double *col(int j) const { return data + (int64_t)j * ld * ed(); }
 };
 
-enum OpKind { OP_DIAG, OP_DIAG_LIN, OP_DENSE, OP_LAP5, OP_GL, OP_CSR };
-struct lk_linop_s {
-    lk_context_t ctx;
-    OpKind kind;
-    int dtype;
-    int64_t n;
-    DevBuf<double> dev;     // diag values / dense matrix (owned, or a view of wrapped caller memory)
-    int64_t lda = 0;
-    // row-sharded dense / CSR: this rank holds rows [rstart[rank], rstart[rank+1]) of an ncols_g x ncols_g operator
-    int64_t ncols_g = 0;                  // global size (= n on a single rank)
-    std::vector<int64_t> gcounts, gdispls;   // all-gather layout in DOUBLES (per rank)
-    DevBuf<double> xfull;                 // the gathered input vector / the full-length adjoint product (ncols_g elements)
-    DevBuf<double> gpart;                 // k_gemv_n's per-chunk partial sums
-    int gchunks = 1;
-    // row-sharded CSR, COMPRESSED exchange: only the entries of x that some other rank's rows reference travel.  cx_send_idx =
-    // local indices of this rank's entries anybody needs (sorted); every rank's packed entries are all-gathered into cx_xrem
-    // (rank r's at cx_displs[r]); the column indices of csr[0] address [own rows | cx_xrem].
-    bool cx = false;
-    DevBuf<int32_t> cx_send_idx;
-    int64_t cx_nsend = 0, cx_total = 0;
-    DevBuf<double> cx_sendbuf, cx_xrem;
-    std::vector<int64_t> cx_counts, cx_displs;   // in DOUBLES, per rank
-    int64_t row0 = 0;
-    double d0 = 0, dstep = 0;
-    int64_t N = 0;
-    // Ginzburg-Landau stepper
-    double gl[8] = {0};   // dx, halfL, nu_re, nu_im, ga_re, ga_im, mu_c, mu2
-    double tau = 0;
-    int nsub = 1;
-    DevBuf<double> wk;    // 3 work vectors (k_a, k_b, u_sub)
-    // row-sharded stencil operators
-    int64_t NJ = 0;            // lap5: grid lines held by this rank
-    int64_t n_global = 0;      // GL: global rows
-    bool has_lo = false, has_hi = false;   // a neighbouring rank below / above this block
-    DevBuf<double> lap5_halo;  // lap5: 2 N doubles (line from rank-1 | line from rank+1)
-    double *halo = nullptr;    // lap5: lap5_halo; GL: 4 doubles inside wk
-    double *edges = nullptr;   // GL: this rank's two edge values (send buffer), 4 doubles inside wk
-    // CSR: A (for 'N') and its conjugate transpose (for 'H'), both row-compressed; W = lanes per row
-    struct Csr {
-        DevBuf<int64_t> rowptr; DevBuf<int32_t> colind; DevBuf<double> vals; int W = 8;
-        DevBuf<int64_t> rowblocks; int64_t nblocks = 0, nnz_hint = 0;   // CSR-stream partition (short rows), see k_csr_stream
-    } csr[2];
-};
-
 namespace {
 
 constexpr int RED_SECTION = (KMAX_FUSED + 1) * 2;  // doubles per result section
@@ -2762,129 +2718,7 @@ int lk_dgs_block(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, double *h,
 }
 
 // ---- operators ------------------------------------------------------------------------------------
-int lk_linop_diag_create(lk_context_t c, int dtype, int64_t n_local, const void *d_host, lk_linop_t *op) {
-    if (!c || !d_host || !op) return fail(LK_ERR_INVALID, "lk_linop_diag_create: null argument");
-    DevGuard dev_guard(c);
-    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "bad dtype");
-    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
-    o->ctx = c; o->kind = OP_DIAG; o->dtype = dtype; o->n = n_local;
-    const int ED = dtype == LK_C128 ? 2 : 1;
-    LKCHK(o->dev.reserve((n_local + 2) * ED));
-    HIPCHK(hipMemcpy(o->dev, d_host, (size_t)n_local * ED * sizeof(double), hipMemcpyHostToDevice));
-    *op = o.release();
-    return LK_OK;
-}
-
-int lk_linop_diag_linspace_create(lk_context_t c, int64_t n_local, int64_t row0, double d0, double dstep, lk_linop_t *op) {
-    if (!c || !op) return fail(LK_ERR_INVALID, "null argument");
-    lk_linop_t o = new lk_linop_s();
-    o->ctx = c; o->kind = OP_DIAG_LIN; o->dtype = LK_F64; o->n = n_local; o->row0 = row0; o->d0 = d0; o->dstep = dstep;
-    *op = o;
-    return LK_OK;
-}
-
-// layout of a row partition for the all-gather of x (counts and displacements in doubles) + the workspaces of a sharded operator
-static int shard_setup(lk_linop_t o, lk_context_t c, int64_t n_global, const int64_t *row_starts, const char *what) {
-    const int ED = o->dtype == LK_C128 ? 2 : 1;
-    if (!row_starts) return fail(LK_ERR_INVALID, "%s: null row_starts", what);
-    if (row_starts[0] != 0 || row_starts[c->nranks] != n_global) return fail(LK_ERR_INVALID, "%s: row_starts must run from 0 to n_global", what);
-    for (int r = 0; r < c->nranks; ++r)
-        if (row_starts[r + 1] < row_starts[r]) return fail(LK_ERR_INVALID, "%s: row_starts decreases at rank %d", what, r);
-    o->ncols_g = n_global;
-    o->n = row_starts[c->rank + 1] - row_starts[c->rank];
-    o->row0 = row_starts[c->rank];
-    o->gcounts.resize(c->nranks);
-    o->gdispls.resize(c->nranks);
-    for (int r = 0; r < c->nranks; ++r) {
-        o->gcounts[r] = (row_starts[r + 1] - row_starts[r]) * ED;
-        o->gdispls[r] = row_starts[r] * ED;
-    }
-    if (c->nranks > 1) LKCHK(o->xfull.reserve((n_global > 0 ? n_global : 1) * ED));
-    return LK_OK;
-}
-
-constexpr int64_t GEMV_COLS_PER_CHUNK = 256;
-
-static int dense_finish(lk_linop_t o, lk_context_t c) {
-    // split-K of y = A x in chunks of GEMV_COLS_PER_CHUNK columns: the chunking depends on the GLOBAL column count only, so a
-    // row's products are added in the same order whatever the row partition (sharded matvec = single-rank matvec bit for bit)
-    (void)c;
-    int64_t chunks = (o->ncols_g + GEMV_COLS_PER_CHUNK - 1) / GEMV_COLS_PER_CHUNK;
-    if (chunks < 1) chunks = 1;
-    o->gchunks = (int)chunks;
-    const int ED = o->dtype == LK_C128 ? 2 : 1;
-    return o->gpart.reserve(chunks * (o->n > 0 ? o->n : 1) * ED);
-}
-
-// the row-sharded dense operator on `A`: the operator's own matrix, or a view of caller memory
-static int dense_build(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, DevBuf<double> A, int64_t lda, lk_linop_t *op) {
-    if (((uintptr_t)(double *)A & 15) != 0) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: pointer must be 16-byte aligned");
-    if (dtype == LK_F64 && (lda & 1)) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda must be even for LK_F64");
-    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
-    o->ctx = c; o->kind = OP_DENSE; o->dtype = dtype; o->dev = std::move(A); o->lda = lda;
-    LKCHK(shard_setup(o.get(), c, n_global, row_starts, "lk_linop_dense_wrap_sharded"));
-    if (lda < o->n) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: lda < local rows");
-    LKCHK(dense_finish(o.get(), c));
-    *op = o.release();
-    return LK_OK;
-}
-
-int lk_linop_dense_wrap_sharded(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, void *dev_ptr, int64_t lda,
-                                lk_linop_t *op) {
-    if (!c || !dev_ptr || !op) return fail(LK_ERR_INVALID, "lk_linop_dense_wrap_sharded: null argument");
-    DevGuard dev_guard(c);
-    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "bad dtype");
-    DevBuf<double> A;
-    A.wrap((double *)dev_ptr);
-    return dense_build(c, dtype, n_global, row_starts, std::move(A), lda, op);
-}
-
-int lk_linop_dense_create_sharded(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, const void *A_rows, int64_t lda,
-                                  lk_linop_t *op) {
-    if (!c || !A_rows || !op || !row_starts) return fail(LK_ERR_INVALID, "lk_linop_dense_create_sharded: null argument");
-    DevGuard dev_guard(c);
-    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "bad dtype");
-    const int64_t n_local = row_starts[c->rank + 1] - row_starts[c->rank];
-    if (n_local < 0 || lda < n_local) return fail(LK_ERR_INVALID, "lk_linop_dense_create_sharded: lda < local rows");
-    const size_t es = (dtype == LK_C128 ? 2 : 1) * sizeof(double);
-    const int64_t ldd = ((n_local + 31) / 32) * 32 + (n_local == 0 ? 32 : 0);          // 256-byte columns on the device
-    DevBuf<double> dev;
-    LKCHK(dev.reserve(ldd * (n_global > 0 ? n_global : 1) * (dtype == LK_C128 ? 2 : 1)));
-    if (n_local > 0 && n_global > 0)
-        HIPCHK(hipMemcpy2D(dev, (size_t)ldd * es, A_rows, (size_t)lda * es, (size_t)n_local * es, n_global, hipMemcpyHostToDevice));
-    return dense_build(c, dtype, n_global, row_starts, std::move(dev), ldd, op);
-}
-
-int lk_linop_dense_create(lk_context_t c, int dtype, int64_t n, const void *A_host, int64_t lda, lk_linop_t *op) {
-    if (!c || !A_host || !op) return fail(LK_ERR_INVALID, "lk_linop_dense_create: null argument");
-    if (lda < n) return fail(LK_ERR_INVALID, "lda < n");
-    if (c->nranks > 1) return fail(LK_ERR_INVALID, "dense_linop over several ranks: use lk_linop_dense_create_sharded (a row block per rank)");
-    const int64_t starts[2] = {0, n};
-    return lk_linop_dense_create_sharded(c, dtype, n, starts, A_host, lda, op);
-}
-
-// x (this rank's rows) -> the operator's full-length buffer, rank r's block at its global offset
-static int gather_x(lk_linop_t op, const double *x, const double **xg) {
-    lk_context_t c = op->ctx;
-    if (c->nranks == 1) { *xg = x; return LK_OK; }
-    if (!c->allgather) return fail(LK_ERR_COMM, "row-sharded dense / CSR operator but no all-gather installed (lk_comm_init_rank / lk_set_allgather)");
-    ProfScope ps(c, "comm_allgather", (double)op->ncols_g * (op->dtype == LK_C128 ? 16.0 : 8.0));
-    const int rc = c->allgather(c->allgather_user, x, op->xfull, op->gcounts.data(), op->gdispls.data(), c->nranks, (void *)c->stream);
-    if (rc != 0) return fail(LK_ERR_COMM, "all-gather callback returned %d", rc);
-    *xg = op->xfull;
-    return LK_OK;
-}
-
-// adjoint products of a row block are full-length partial sums: summed over the ranks, then this rank keeps its own rows
-static int reduce_to_slice(lk_linop_t op, double *zfull, double *y) {
-    lk_context_t c = op->ctx;
-    const int ED = op->dtype == LK_C128 ? 2 : 1;
-    LKCHK(allreduce(c, zfull, op->ncols_g * ED));
-    const int64_t nd = op->n * ED;
-    hipLaunchKernelGGL(k_copy_guarded, dim3(blas1_grid(c, nd / 2 + 1)), dim3(256), 0, c->stream, (const double *)(zfull + op->row0 * ED), y, nd, c->guard());
-    HIPCHK(hipGetLastError());
-    return LK_OK;
-}
+#include "lk_operators.hip.h"
 
 int lk_set_allgather(lk_context_t c, lk_allgather_fn fn, void *user) {
     if (!c) return fail(LK_ERR_INVALID, "lk_set_allgather: null context");
@@ -2893,508 +2727,10 @@ int lk_set_allgather(lk_context_t c, lk_allgather_fn fn, void *user) {
     return LK_OK;
 }
 
-static int halo_exchange(lk_context_t c, const double *send_lo, const double *send_hi, double *recv_lo, double *recv_hi, int64_t count) {
-    if (!c->halo) return fail(LK_ERR_COMM, "row-sharded stencil operator but no halo exchange installed (lk_comm_init_rank / lk_set_halo_exchange)");
-    ProfScope ps(c, "comm_halo", (double)count * 8.0 * ((send_lo ? 1 : 0) + (send_hi ? 1 : 0)));
-    const int rc = c->halo(c->halo_user, send_lo, send_hi, recv_lo, recv_hi, count, (void *)c->stream);
-    if (rc != 0) return fail(LK_ERR_COMM, "halo exchange callback returned %d", rc);
-    return LK_OK;
-}
-
 int lk_set_halo_exchange(lk_context_t c, lk_halo_fn fn, void *user) {
     if (!c) return fail(LK_ERR_INVALID, "lk_set_halo_exchange: null context");
     c->halo = fn;
     c->halo_user = user;
-    return LK_OK;
-}
-
-int lk_linop_lap5_create_sharded(lk_context_t c, int64_t N, int64_t j0, int64_t nj, lk_linop_t *op) {
-    if (!c || !op || N < 1 || j0 < 0 || nj < 1 || j0 + nj > N) return fail(LK_ERR_INVALID, "lk_linop_lap5_create: bad argument");
-    DevGuard dev_guard(c);
-    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
-    o->ctx = c; o->kind = OP_LAP5; o->dtype = LK_F64; o->n = nj * N; o->N = N; o->NJ = nj;
-    o->has_lo = j0 > 0; o->has_hi = j0 + nj < N;
-    // the halo exchange addresses its peers by RANK ORDER (rank - 1 below, rank + 1 above): a partition that does not follow
-    // it would skip a send on one side and leave the neighbour waiting
-    if (c->nranks > 1 && (o->has_lo != (c->rank > 0) || o->has_hi != (c->rank < c->nranks - 1))) {
-        return fail(LK_ERR_INVALID, "lk_linop_lap5_create_sharded: grid lines [%lld, %lld) of %lld on rank %d/%d do not follow rank order "
-                    "(rank r must own the r-th consecutive block)", (long long)j0, (long long)(j0 + nj), (long long)N, c->rank, c->nranks);
-    }
-    if (o->has_lo || o->has_hi) {
-        LKCHK(o->lap5_halo.reserve(2 * N));
-        o->halo = o->lap5_halo;
-    }
-    *op = o.release();
-    return LK_OK;
-}
-
-int lk_linop_lap5_create(lk_context_t c, int64_t N, lk_linop_t *op) {
-    if (c && c->nranks > 1) return fail(LK_ERR_INVALID, "lap5 over several ranks: use lk_linop_lap5_create_sharded (grid lines per rank)");
-    return lk_linop_lap5_create_sharded(c, N, 0, N, op);
-}
-
-int lk_linop_gl_create_sharded(lk_context_t c, int64_t n_global, int64_t row0, int64_t n_local, double dx, double tau, int nsub,
-                               const double *nu, const double *gamma, double mu_c, double mu2, lk_linop_t *op) {
-    if (!c || !op || !nu || !gamma || n_global < 1 || n_local < 1 || row0 < 0 || row0 + n_local > n_global || nsub < 1 || !(dx > 0.0))
-        return fail(LK_ERR_INVALID, "lk_linop_gl_create: bad argument");
-    DevGuard dev_guard(c);
-    std::unique_ptr<lk_linop_s> o(new lk_linop_s());
-    o->ctx = c; o->kind = OP_GL; o->dtype = LK_C128; o->n = n_local; o->tau = tau; o->nsub = nsub;
-    o->row0 = row0; o->n_global = n_global;
-    o->has_lo = row0 > 0; o->has_hi = row0 + n_local < n_global;
-    if (c->nranks > 1 && (o->has_lo != (c->rank > 0) || o->has_hi != (c->rank < c->nranks - 1))) {
-        return fail(LK_ERR_INVALID, "lk_linop_gl_create_sharded: rows [%lld, %lld) of %lld on rank %d/%d do not follow rank order "
-                    "(rank r must own the r-th consecutive block)", (long long)row0, (long long)(row0 + n_local), (long long)n_global, c->rank, c->nranks);
-    }
-    o->gl[0] = dx; o->gl[1] = 0.5 * dx * (double)(n_global + 1);   // L = dx (n+1), x = linspace(-L/2, L/2, n+2)
-    o->gl[2] = nu[0]; o->gl[3] = nu[1]; o->gl[4] = gamma[0]; o->gl[5] = gamma[1]; o->gl[6] = mu_c; o->gl[7] = mu2;
-    LKCHK(o->wk.reserve(3 * n_local * 2 + 8));
-    o->halo = o->wk + (size_t)6 * n_local;      // 4 doubles
-    o->edges = o->halo + 4;                     // 4 doubles
-    (void)hipMemsetAsync(o->halo, 0, 8 * sizeof(double), c->stream);
-    *op = o.release();
-    return LK_OK;
-}
-
-int lk_linop_gl_create(lk_context_t c, int64_t n, double dx, double tau, int nsub, const double *nu, const double *gamma,
-                       double mu_c, double mu2, lk_linop_t *op) {
-    if (c && c->nranks > 1) return fail(LK_ERR_INVALID, "Ginzburg-Landau operator over several ranks: use lk_linop_gl_create_sharded");
-    return lk_linop_gl_create_sharded(c, n, 0, n, dx, tau, nsub, nu, gamma, mu_c, mu2, op);
-}
-
-// A = (rowptr, colind, vals) in CSR, 0-based; `which` = 0 stores A itself, 1 its conjugate transpose (built on the host by a
-// counting sort: column indices within a row of A^H come out ascending, so both products sum in index order).
-static int csr_upload(lk_linop_t o, int which, int64_t n, const int64_t *rowptr, const int32_t *colind, const double *vals, int ED) {
-    const int64_t nnz = rowptr[n];
-    auto &m = o->csr[which];
-    LKCHK(m.rowptr.reserve(n + 1));
-    LKCHK(m.colind.reserve(nnz > 0 ? nnz : 1));
-    LKCHK(m.vals.reserve((nnz > 0 ? nnz : 1) * ED));
-    HIPCHK(hipMemcpy(m.rowptr, rowptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (nnz > 0) {
-        HIPCHK(hipMemcpy(m.colind, colind, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(m.vals, vals, (size_t)nnz * ED * sizeof(double), hipMemcpyHostToDevice));
-    }
-    {   // CSR-stream partition: consecutive rows, at most CSR_NNZ entries and 256 rows per block; a longer row stands alone
-        std::vector<int64_t> rb;
-        rb.push_back(0);
-        int64_t r = 0;
-        while (r < n) {
-            int64_t e = r + 1;                                              // at least one row, however long
-            while (e < n && e - r < 256 && rowptr[e + 1] - rowptr[r] <= CSR_NNZ) ++e;
-            rb.push_back(e);
-            r = e;
-        }
-        m.nblocks = (int64_t)rb.size() - 1;
-        LKCHK(m.rowblocks.reserve((int64_t)rb.size()));
-        HIPCHK(hipMemcpy(m.rowblocks, rb.data(), rb.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    m.nnz_hint = nnz;
-    const double mean = n > 0 ? (double)nnz / (double)n : 0.0;
-    int W = 1;                                   // lanes per row: the power of two at or below half the mean row length
-    while (W < 64 && 2 * W <= mean / 2.0) W <<= 1;   // (5-point Laplacian, n = 1.7e7: W = 1 / 2 / 4 / 8 / 16 -> see DESIGN.md)
-    m.W = W;
-    return LK_OK;
-}
-
-// creation-time metadata exchange through the data-path hook: every rank contributes `mine` (counts[rank] doubles), all receive all
-static int host_allgatherv(lk_context_t c, const std::vector<double> &mine, const std::vector<int64_t> &counts, std::vector<double> &all) {
-    std::vector<int64_t> displs(c->nranks, 0);
-    int64_t total = 0;
-    for (int r = 0; r < c->nranks; ++r) { displs[r] = total; total += counts[r]; }
-    all.assign((size_t)total, 0.0);
-    if (total == 0) return LK_OK;
-    if (!c->allgather) return fail(LK_ERR_COMM, "row-sharded CSR operator but no all-gather installed (lk_comm_init_rank / lk_set_allgather)");
-    DevBuf<double> ds, dr;
-    LKCHK(ds.reserve(mine.size() > 0 ? (int64_t)mine.size() : 1));
-    LKCHK(dr.reserve(total));
-    int rc = LK_OK;
-    if (!mine.empty() && hipMemcpyAsync(ds, mine.data(), mine.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "metadata upload failed");
-    if (rc == LK_OK && c->allgather(c->allgather_user, ds, dr, counts.data(), displs.data(), c->nranks, (void *)c->stream) != 0)
-        rc = fail(LK_ERR_COMM, "all-gather callback failed (metadata)");
-    if (rc == LK_OK && hipMemcpyAsync(all.data(), dr, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "metadata download failed");
-    if (rc == LK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(LK_ERR_HIP, "stream synchronisation failed");
-    return rc;
-}
-
-// A COLLECTIVE creation routine must not leave a rank behind: a rank that returned early (a bad column index, a failed
-// allocation) would let the others wait for it in the next exchange for ever.  Every rank contributes its local status; when any
-// rank failed, EVERY rank returns an error -- its own where it has one, otherwise one naming the first rank that failed.  One
-// tiny all-gather through the data-path hook + a stream synchronisation: creation time only.
-static int agree_status(lk_context_t c, int rc_local, const char *what) {
-    if (c->nranks <= 1) return rc_local;
-    std::vector<double> mine(1, (double)rc_local), all;
-    const int xrc = host_allgatherv(c, mine, std::vector<int64_t>((size_t)c->nranks, 1), all);
-    if (xrc != LK_OK) return rc_local != LK_OK ? rc_local : xrc;
-    if (rc_local != LK_OK) return rc_local;                   // lk_last_error already says why
-    for (int r = 0; r < c->nranks; ++r)
-        if (all[(size_t)r] != 0.0)
-            return fail(LK_ERR_COMM, "%s: rank %d failed (status %d); every rank returns without the operator", what, r, (int)all[(size_t)r]);
-    return LK_OK;
-}
-
-// Decide and set up the compressed exchange of a row-sharded CSR operator (COLLECTIVE: every rank calls it at creation).  On
-// return `cols` holds the column indices csr[0] is uploaded with: remapped to [own rows | packed remote entries] when o->cx, the
-// global ones otherwise.  The exchange is compressed when what travels is less than half of x (stencils, banded matrices: a few
-// boundary entries per neighbour); matrices whose rows reach everywhere keep the plain all-gather of x.
-static int csr_compress_setup(lk_linop_t o, lk_context_t c, const int64_t *row_starts, int64_t n, const int64_t *rowptr, const int32_t *colind,
-                              std::vector<int32_t> &cols) {
-    const int P = c->nranks, me = c->rank;
-    const int ED = o->dtype == LK_C128 ? 2 : 1;
-    const int64_t nnz = rowptr[n], row0 = row_starts[me], n_global = row_starts[P];
-    cols.assign(colind, colind + nnz);
-    if (P == 1) return LK_OK;
-    auto owner = [&](int64_t j) {                        // rank whose block holds global row j
-        int lo = 0, hi = P - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row_starts[mid] <= j) lo = mid; else hi = mid - 1; }
-        while (lo + 1 < P && row_starts[lo + 1] <= j) ++lo;      // empty blocks share a start
-        return lo;
-    };
-    // what I need from whom: the out-of-block column indices, sorted and unique -- owners hold contiguous row ranges, so the
-    // sorted list falls apart into one run per owner (4 bytes per remote entry of transient memory, no per-owner vectors)
-    std::vector<int32_t> rem;
-    for (int64_t p = 0; p < nnz; ++p) {
-        const int64_t j = colind[p];
-        if (j < row0 || j >= row0 + n) rem.push_back((int32_t)j);
-    }
-    std::sort(rem.begin(), rem.end());
-    rem.erase(std::unique(rem.begin(), rem.end()), rem.end());
-    std::vector<std::vector<int64_t>> need(P);
-    for (int32_t j : rem) need[owner(j)].push_back(j);
-    std::vector<int32_t>().swap(rem);
-    // everybody learns everybody's request COUNTS (a P x P table); the lists themselves travel only when the compressed exchange
-    // can still pay off: what anybody needs of rank r's block is at least the longest single request for it, so
-    // 2 * sum_r max_q count[q][r] >= n_global already means "half of x or more travels anyway" -- decided from the table every
-    // rank holds identically, before the O(P * requests) exchange of the lists (matrices whose rows reach widely)
-    std::vector<double> mycnt(P), allcnt;
-    for (int r = 0; r < P; ++r) mycnt[r] = (double)need[r].size();
-    LKCHK(host_allgatherv(c, mycnt, std::vector<int64_t>(P, P), allcnt));
-    int64_t maxn = 0;
-    for (int r = 0; r < P; ++r) maxn = std::max(maxn, row_starts[r + 1] - row_starts[r]);
-    {
-        int64_t lower = 0;
-        for (int r = 0; r < P; ++r) {
-            int64_t mx = 0;
-            for (int q = 0; q < P; ++q) mx = std::max(mx, (int64_t)allcnt[(size_t)q * P + r]);
-            lower += mx;
-        }
-        if (2 * lower >= n_global) return LK_OK;
-    }
-    std::vector<int64_t> listlen(P, 0);
-    for (int q = 0; q < P; ++q) for (int r = 0; r < P; ++r) listlen[q] += (int64_t)allcnt[(size_t)q * P + r];
-    std::vector<double> mylist, alllist;
-    for (int r = 0; r < P; ++r) for (int64_t j : need[r]) mylist.push_back((double)j);
-    LKCHK(host_allgatherv(c, mylist, listlen, alllist));
-    // S_r = what anybody needs of rank r's block (sorted, unique): the packed buffer rank r contributes per matvec
-    std::vector<std::vector<int64_t>> S(P);
-    {
-        size_t pos = 0;
-        for (int q = 0; q < P; ++q)
-            for (int r = 0; r < P; ++r) {
-                const int64_t cnt = (int64_t)allcnt[(size_t)q * P + r];
-                for (int64_t i = 0; i < cnt; ++i) S[r].push_back((int64_t)alllist[pos + (size_t)i]);
-                pos += (size_t)cnt;
-            }
-        for (auto &v : S) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
-    }
-    int64_t total = 0;
-    for (int r = 0; r < P; ++r) total += (int64_t)S[r].size();
-    // nearly all of x travels anyway, or the remapped indices would not fit: plain all-gather.  Decided from quantities every rank
-    // holds identically (a rank that chose differently would issue a different collective)
-    if (2 * total >= n_global || maxn + total > 2147483647LL) return LK_OK;
-    o->cx = true;
-    o->cx_total = total;
-    o->cx_counts.resize(P); o->cx_displs.resize(P);
-    std::vector<int64_t> off(P, 0);
-    { int64_t a = 0; for (int r = 0; r < P; ++r) { off[r] = a; o->cx_counts[r] = (int64_t)S[r].size() * ED; o->cx_displs[r] = a * ED; a += (int64_t)S[r].size(); } }
-    for (int64_t p = 0; p < nnz; ++p) {
-        const int64_t j = colind[p];
-        if (j >= row0 && j < row0 + n) { cols[(size_t)p] = (int32_t)(j - row0); continue; }
-        const int r = owner(j);
-        const int64_t k = std::lower_bound(S[r].begin(), S[r].end(), j) - S[r].begin();
-        cols[(size_t)p] = (int32_t)(n + off[r] + k);
-    }
-    o->cx_nsend = (int64_t)S[me].size();
-    std::vector<int32_t> sidx((size_t)(o->cx_nsend > 0 ? o->cx_nsend : 1), 0);
-    for (int64_t i = 0; i < o->cx_nsend; ++i) sidx[(size_t)i] = (int32_t)(S[me][(size_t)i] - row0);
-    LKCHK(o->cx_send_idx.reserve((int64_t)sidx.size()));
-    HIPCHK(hipMemcpy(o->cx_send_idx, sidx.data(), sidx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    LKCHK(o->cx_sendbuf.reserve((o->cx_nsend > 0 ? o->cx_nsend : 1) * ED));
-    return o->cx_xrem.reserve((total > 0 ? total : 1) * ED);
-}
-
-// local (rank-private) validation of a row block: nothing here talks to another rank
-static int csr_validate_rows(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, const int64_t *rowptr, const int32_t *colind,
-                             const void *vals) {
-    if (!rowptr) return fail(LK_ERR_INVALID, "lk_linop_csr_create: null rowptr (this rank's row block was rejected by the caller)");
-    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "lk_linop_csr_create: bad dtype %d", dtype);
-    if (n_global < 0 || n_global > 2147483647LL) return fail(LK_ERR_INVALID, "lk_linop_csr_create: bad size %lld", (long long)n_global);
-    const int64_t n = row_starts[c->rank + 1] - row_starts[c->rank];      // rows held here; column indices are GLOBAL
-    if (n < 0) return fail(LK_ERR_INVALID, "lk_linop_csr_create: row_starts decreases");
-    if (rowptr[0] != 0) return fail(LK_ERR_INVALID, "lk_linop_csr_create: rowptr must be 0-based");
-    for (int64_t i = 0; i < n; ++i)
-        if (rowptr[i + 1] < rowptr[i]) return fail(LK_ERR_INVALID, "lk_linop_csr_create: rowptr decreases at row %lld", (long long)i);
-    const int64_t nnz = rowptr[n];
-    if (nnz > 0 && (!colind || !vals)) return fail(LK_ERR_INVALID, "lk_linop_csr_create: null colind / vals");
-    for (int64_t p = 0; p < nnz; ++p)
-        if (colind[p] < 0 || colind[p] >= n_global) return fail(LK_ERR_INVALID, "lk_linop_csr_create: column index %d out of range at entry %lld", colind[p], (long long)p);
-    return LK_OK;
-}
-
-int lk_linop_csr_create_sharded(lk_context_t c, int dtype, int64_t n_global, const int64_t *row_starts, const int64_t *rowptr,
-                                const int32_t *colind, const void *vals, lk_linop_t *op) {
-    // a null context / result / partition is a programming error of the call site, identical on every rank: plain early return.
-    // A null rowptr is NOT: it is how a host-side wrapper that found this rank's input unusable (wrong number of rows, wrong
-    // value type) still joins the agreement below, so that every rank fails together (lightkrylov_amd/linops.py).
-    if (!c || !op || !row_starts) return fail(LK_ERR_INVALID, "lk_linop_csr_create: null argument");
-    DevGuard dev_guard(c);
-    // COLLECTIVE from here on.  Everything that can fail on ONE rank only (this rank's rows, this rank's allocations) is agreed
-    // on before the next exchange is entered: first the validation of the row block ...
-    LKCHK(agree_status(c, csr_validate_rows(c, dtype, n_global, row_starts, rowptr, colind, vals), "lk_linop_csr_create_sharded (validation)"));
-    const int64_t n = row_starts[c->rank + 1] - row_starts[c->rank];
-    const int64_t nnz = rowptr[n];
-    const int ED = dtype == LK_C128 ? 2 : 1;
-    const double *v = (const double *)vals;
-    // conjugate transpose of the row block (n_global rows, LOCAL column indices) by counting sort over the column indices.  Host
-    // allocations of THIS rank (n_global + nnz entries): a bad_alloc must neither cross the C ABI nor leave the peers in the next
-    // exchange -- it becomes this rank's status in the "buffers" agreement below
-    std::vector<int64_t> tp;
-    std::vector<int32_t> tc;
-    std::vector<double> tv;
-    std::unique_ptr<lk_linop_s> o;
-    int rc_host = LK_OK;
-    try {
-        tp.assign((size_t)n_global + 1, 0);
-        for (int64_t p = 0; p < nnz; ++p) tp[(size_t)colind[p] + 1] += 1;
-        for (int64_t j = 0; j < n_global; ++j) tp[(size_t)j + 1] += tp[(size_t)j];
-        tc.resize((size_t)(nnz > 0 ? nnz : 1));
-        tv.resize((size_t)(nnz > 0 ? nnz : 1) * ED);
-        std::vector<int64_t> next(tp.begin(), tp.end() - 1);
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t p = rowptr[i]; p < rowptr[i + 1]; ++p) {
-                const int64_t q = next[(size_t)colind[p]]++;
-                tc[(size_t)q] = (int32_t)i;
-                tv[(size_t)q * ED] = v[p * ED];
-                if (ED == 2) tv[(size_t)q * 2 + 1] = -v[p * 2 + 1];
-            }
-        o.reset(new lk_linop_s());
-        o->ctx = c; o->kind = OP_CSR; o->dtype = dtype;
-    } catch (const std::exception &e) {
-        rc_host = fail(LK_ERR_NOMEM, "lk_linop_csr_create_sharded: host allocation failed while transposing this rank's rows (%s)", e.what());
-    }
-    // ... then this rank's share of the set-up that precedes the metadata exchange (the transpose above, the gathered-x buffer) ...
-    int rc = agree_status(c, rc_host != LK_OK ? rc_host : shard_setup(o.get(), c, n_global, row_starts, "lk_linop_csr_create"), "lk_linop_csr_create_sharded (buffers)");
-    if (rc == LK_OK) {
-        // ... the metadata exchange itself (its decisions come from quantities every rank holds identically; its staging buffers
-        // are a few P-length tables and the request lists -- a rank that cannot allocate THOSE is fatal for the job, see header) ...
-        try {
-            std::vector<int32_t> cols0;
-            rc = csr_compress_setup(o.get(), c, row_starts, n, rowptr, colind, cols0);
-            if (rc == LK_OK) rc = csr_upload(o.get(), 0, n, rowptr, cols0.data(), v, ED);
-            if (rc == LK_OK) rc = csr_upload(o.get(), 1, n_global, tp.data(), tc.data(), tv.data(), ED);
-        } catch (const std::exception &e) {
-            rc = fail(LK_ERR_NOMEM, "lk_linop_csr_create_sharded: host allocation failed (%s)", e.what());
-        }
-        // ... and finally the uploads: an operator exists on every rank or on none
-        rc = agree_status(c, rc, "lk_linop_csr_create_sharded (upload)");
-    }
-    if (rc != LK_OK) return rc;
-    *op = o.release();
-    return LK_OK;
-}
-
-int lk_linop_csr_create(lk_context_t c, int dtype, int64_t n, const int64_t *rowptr, const int32_t *colind, const void *vals,
-                        lk_linop_t *op) {
-    if (!c || !rowptr || !op) return fail(LK_ERR_INVALID, "lk_linop_csr_create: null argument");
-    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_linop_csr_create over several ranks: use lk_linop_csr_create_sharded (a row block per rank)");
-    const int64_t starts[2] = {0, n};
-    return lk_linop_csr_create_sharded(c, dtype, n, starts, rowptr, colind, vals, op);
-}
-
-int lk_linop_destroy(lk_linop_t op) {
-    delete op;   // what the operator owns goes with it (the frees synchronise); op->ctx may already be finalized and is not touched
-    return LK_OK;
-}
-
-int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t By, int jy) {
-    if (!op) return fail(LK_ERR_INVALID, "lk_linop_apply: null operator");
-    DevGuard dev_guard(op->ctx);
-    LKCHK(check_vec(Bx, jx, "lk_linop_apply(vec_in)"));
-    LKCHK(check_vec(By, jy, "lk_linop_apply(vec_out)"));
-    LKCHK(check_pair(Bx, By, "lk_linop_apply"));
-    if (Bx->dtype != op->dtype || Bx->n != op->n) return fail(LK_ERR_INVALID, "lk_linop_apply: operator/vector mismatch");
-    lk_context_t c = op->ctx;
-    const double *x = Bx->col(jx);
-    double *y = By->col(jy);
-    if (x == y) return fail(LK_ERR_INVALID, "lk_linop_apply: vec_in and vec_out alias");
-    {
-        const VecRef w{By, jy}, r{Bx, jx};
-        LKCHK(lazy_enter_vec(c, &w, true, &r, nullptr));       // vec_out is intent(out): AbstractLinops.fypp:74-87
-    }
-    By->touch(jy);
-    const bool cp = op->dtype == LK_C128;
-    const int64_t n = op->n;
-    const int64_t nv = n * Bx->ed() / 2 + 1;
-    // algorithmic bytes of the operator (diagonal: d, x read, y written; generated diagonal: x read, y written); 0 = not priced
-    const double mv_bytes = op->kind == OP_DIAG ? 3.0 * n * Bx->ed() * 8.0 : (op->kind == OP_DIAG_LIN ? 2.0 * n * 8.0 : 0.0);
-    // the diagonal operators (one kernel) carry their two events on the dispatch itself, like the sweeps: no marker packets
-    const bool one_kernel = op->kind == OP_DIAG || op->kind == OP_DIAG_LIN;
-    ProfScope ps(c, "matvec", mv_bytes, one_kernel && c->prof_ext);
-    switch (op->kind) {
-    case OP_DIAG:
-        if (ps.on && ps.ext) {
-            if (cp) hipExtLaunchKernelGGL(k_diag<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, (const double *)op->dev, x, y, n, (int)(trans == LK_OP_H), c->guard());
-            else hipExtLaunchKernelGGL(k_diag<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, (const double *)op->dev, x, y, n, 0, c->guard());
-            break;
-        }
-        if (cp) hipLaunchKernelGGL(k_diag<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, op->dev, x, y, n, trans == LK_OP_H, c->guard());
-        else hipLaunchKernelGGL(k_diag<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, op->dev, x, y, n, 0, c->guard());
-        break;
-    case OP_DIAG_LIN:
-        if (ps.on && ps.ext)
-            hipExtLaunchKernelGGL(k_diag_linspace, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, op->d0, op->dstep, op->row0, x, y, n, c->guard());
-        else
-            hipLaunchKernelGGL(k_diag_linspace, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, op->d0, op->dstep, op->row0, x, y, n, c->guard());
-        break;
-    case OP_DENSE: {
-        const int ED = Bx->ed();
-        if (trans == LK_OP_N) {
-            const double *xg = nullptr;
-            LKCHK(gather_x(op, x, &xg));                                                  // sharded: all-gather of x
-            const int64_t cpc = GEMV_COLS_PER_CHUNK;
-            const dim3 grid((unsigned)((n + (cp ? 255 : 511)) / (cp ? 256 : 512)), (unsigned)op->gchunks);
-            if (n > 0) {
-                if (cp) hipLaunchKernelGGL(k_gemv_n<true>, grid, dim3(256), 0, c->stream, op->dev, op->lda, n, op->ncols_g, xg, op->gpart, cpc, c->guard());
-                else hipLaunchKernelGGL(k_gemv_n<false>, grid, dim3(256), 0, c->stream, op->dev, op->lda, n, op->ncols_g, xg, op->gpart, cpc, c->guard());
-                hipLaunchKernelGGL(k_gemv_n_finish, dim3(blas1_grid(c, n * ED)), dim3(256), 0, c->stream, (const double *)op->gpart, n * ED, op->gchunks, y, c->guard());
-            }
-        } else {
-            // y = A^H x.  Sharded: z = A_rows^H x_rows has n_global entries on every rank; their sum over the ranks is the
-            // product, of which this rank keeps its rows.
-            double *z = c->nranks > 1 ? op->xfull : y;
-            if (op->ncols_g > 0) {
-                if (cp) hipLaunchKernelGGL(k_gemv_h<true>, dim3((unsigned)((op->ncols_g + 3) / 4)), dim3(256), 0, c->stream, op->dev, op->lda, n, op->ncols_g, x, z, c->guard());
-                else hipLaunchKernelGGL(k_gemv_h<false>, dim3((unsigned)((op->ncols_g + 3) / 4)), dim3(256), 0, c->stream, op->dev, op->lda, n, op->ncols_g, x, z, c->guard());
-            }
-            if (c->nranks > 1) LKCHK(reduce_to_slice(op, z, y));
-        }
-        break;
-    }
-    case OP_CSR: {
-        const auto &m = op->csr[trans == LK_OP_N ? 0 : 1];
-        const int W = c->csr_lanes ? c->csr_lanes : m.W;                 // (a forced lane count is never written into the operator)
-        // row-sharded: 'N' multiplies this rank's rows with the all-gathered x; 'H' applies the conjugate transpose of the row
-        // block (n_global rows) to this rank's x, sums the full-length results over the ranks and keeps this rank's rows
-        const bool shard = c->nranks > 1;
-        const int64_t nr = trans == LK_OP_N ? n : op->ncols_g;          // rows of the product computed here
-        const double *xin = x;
-        double *yout = y;
-        const double *xrem = nullptr;
-        int64_t nloc = INT64_MAX;                                        // column indices below nloc address `xin`, the others `xrem`
-        if (shard && trans == LK_OP_N && op->cx) {
-            // compressed exchange: pack what other ranks' rows reference, all-gather the packed pieces, multiply [own rows | pieces]
-            if (!c->allgather) return fail(LK_ERR_COMM, "row-sharded CSR operator but no all-gather installed (lk_comm_init_rank / lk_set_allgather)");
-            if (op->cx_nsend > 0) {
-                if (cp) hipLaunchKernelGGL(k_pack<true>, dim3(blas1_grid(c, op->cx_nsend)), dim3(256), 0, c->stream, x, op->cx_send_idx, op->cx_nsend, op->cx_sendbuf, c->guard());
-                else hipLaunchKernelGGL(k_pack<false>, dim3(blas1_grid(c, op->cx_nsend)), dim3(256), 0, c->stream, x, op->cx_send_idx, op->cx_nsend, op->cx_sendbuf, c->guard());
-                HIPCHK(hipGetLastError());
-            }
-            {
-                ProfScope ps(c, "comm_allgather", (double)op->cx_total * (cp ? 16.0 : 8.0));
-                if (c->allgather(c->allgather_user, op->cx_sendbuf, op->cx_xrem, op->cx_counts.data(), op->cx_displs.data(), c->nranks, (void *)c->stream) != 0)
-                    return fail(LK_ERR_COMM, "all-gather callback failed");
-            }
-            xrem = op->cx_xrem;
-            nloc = n;
-        } else if (shard && trans == LK_OP_N) {
-            LKCHK(gather_x(op, x, &xin));
-        }
-        if (shard && trans != LK_OP_N) yout = op->xfull;
-        bool launched = false;
-        if (c->csr_stream && nr > 0 && (double)m.nnz_hint / (double)nr <= 32.0 && !c->csr_lanes) {
-            // short rows: stream the entries through LDS (k_csr_stream)
-            int64_t g = m.nblocks;
-            const int64_t cap = (int64_t)c->num_cu * 16;
-            if (g > cap) g = cap;
-            if (g < 1) g = 1;
-            if (cp) hipLaunchKernelGGL(k_csr_stream<true>, dim3((unsigned)g), dim3(256), 0, c->stream, m.rowblocks, m.rowptr, m.colind, m.vals, xin, yout, m.nblocks, c->guard(), xrem, nloc);
-            else hipLaunchKernelGGL(k_csr_stream<false>, dim3((unsigned)g), dim3(256), 0, c->stream, m.rowblocks, m.rowptr, m.colind, m.vals, xin, yout, m.nblocks, c->guard(), xrem, nloc);
-            launched = true;
-        }
-        if (!launched) {
-            const int64_t rows_per_block = 256 / W;
-            int64_t g = (nr + rows_per_block - 1) / rows_per_block;
-            const int64_t cap = (int64_t)c->num_cu * 16;
-            if (g > cap) g = cap;
-            if (g < 1) g = 1;
-#define LK_CSR_LAUNCH(WW)                                                                                                  \
-    case WW:                                                                                                               \
-        if (cp) hipLaunchKernelGGL((k_csr<true, WW>), dim3((unsigned)g), dim3(256), 0, c->stream, m.rowptr, m.colind, m.vals, xin, yout, nr, c->guard(), xrem, nloc); \
-        else hipLaunchKernelGGL((k_csr<false, WW>), dim3((unsigned)g), dim3(256), 0, c->stream, m.rowptr, m.colind, m.vals, xin, yout, nr, c->guard(), xrem, nloc);   \
-        break;
-            switch (W) {
-                LK_CSR_LAUNCH(1) LK_CSR_LAUNCH(2) LK_CSR_LAUNCH(4) LK_CSR_LAUNCH(8) LK_CSR_LAUNCH(16) LK_CSR_LAUNCH(32) LK_CSR_LAUNCH(64)
-            default: return fail(LK_ERR_INVALID, "internal: CSR lanes per row %d", W);
-            }
-#undef LK_CSR_LAUNCH
-        }
-        HIPCHK(hipGetLastError());
-        if (shard && trans != LK_OP_N) LKCHK(reduce_to_slice(op, yout, y));
-        break;
-    }
-    case OP_GL: {
-        // nsub classical RK4 steps of dt = tau/nsub; 4 stage launches per step.
-        const double dt = op->tau / op->nsub;
-        const double *g = op->gl;
-        double *ka = op->wk, *kb = op->wk + 2 * n, *us = op->wk + 4 * n;
-        const unsigned grid = (unsigned)((n + 255) / 256);
-        const int adj = trans == LK_OP_H;
-        const double *uin = x;
-        for (int sstep = 0; sstep < op->nsub; ++sstep) {
-            // outputs alternate between the work vector and y so that the LAST sub-step lands in y
-            double *uout = ((op->nsub - 1 - sstep) % 2 == 0) ? y : us;
-            const bool sharded = op->has_lo || op->has_hi;
-            const double *halo = sharded ? op->halo : nullptr;
-#define GL_STAGE(KPREV, A, KOUT, B, FIRST)                                                                                    \
-            do {                                                                                                                   \
-                if (sharded) {   /* the stage needs v = u + a*kprev one point beyond either end of this rank's block */          \
-                    hipLaunchKernelGGL(k_gl_edges, dim3(1), dim3(64), 0, c->stream, uin, KPREV, A, n, op->edges, c->guard());      \
-                    LKCHK(halo_exchange(c, op->has_lo ? op->edges : nullptr, op->has_hi ? op->edges + 2 : nullptr,                \
-                                        op->has_lo ? op->halo : nullptr, op->has_hi ? op->halo + 2 : nullptr, 2));               \
-                }                                                                                                                  \
-                hipLaunchKernelGGL(k_gl_stage, dim3(grid), dim3(256), 0, c->stream, uin, KPREV, A, KOUT, uout, B, FIRST, n, g[0], g[1], \
-                                   g[2], g[3], g[4], g[5], g[6], g[7], adj, op->row0, op->n_global, halo, c->guard());            \
-            } while (0)
-            GL_STAGE((const double *)nullptr, 0.0, ka, dt / 6.0, 1);
-            GL_STAGE((const double *)ka, 0.5 * dt, kb, dt / 3.0, 0);
-            GL_STAGE((const double *)kb, 0.5 * dt, ka, dt / 3.0, 0);
-            GL_STAGE((const double *)ka, dt, kb, dt / 6.0, 0);
-#undef GL_STAGE
-            uin = uout;
-        }
-        break;
-    }
-    case OP_LAP5: {
-        const int64_t N = op->N, NJ = op->NJ;
-        const double s = (double)(N + 1) * (double)(N + 1);
-        const double *lo = nullptr, *hi = nullptr;
-        if (op->has_lo || op->has_hi) {
-            // first / last local grid line to the neighbouring ranks, theirs into the halo buffer (N doubles each)
-            lo = op->has_lo ? op->halo : nullptr;
-            hi = op->has_hi ? op->halo + N : nullptr;
-            LKCHK(halo_exchange(c, op->has_lo ? x : nullptr, op->has_hi ? x + (NJ - 1) * N : nullptr, op->has_lo ? op->halo : nullptr,
-                                op->has_hi ? op->halo + N : nullptr, N));
-        }
-        dim3 grid((unsigned)((N / 2 + 1 + 255) / 256), (unsigned)NJ);
-        if ((N & 1) == 0) {                               // persistent blocks over (line, segment) tiles
-            int64_t tiles = NJ * ((N / 2 + 255) / 256), g = (int64_t)c->num_cu * c->lap5_grid_mult;
-            grid = dim3((unsigned)(tiles < g ? (tiles > 0 ? tiles : 1) : g), 1);
-        }
-        hipLaunchKernelGGL(k_lap5, grid, dim3(256), 0, c->stream, x, y, N, NJ, lo, hi, s, c->guard());
-        break;
-    }
-    }
-    HIPCHK(hipGetLastError());
     return LK_OK;
 }
 
@@ -3454,12 +2790,7 @@ static RowOp fused_rowop(lk_linop_t A, lk_basis_t X, int k, int trans) {
     RowOp r{};
     if (!c->fuse_rowop || !c->recompute_update || c->stream_two || A->dtype != X->dtype || A->n != X->n) return r;
     if (X->dtype == LK_C128 && k > KMAX_FUSED) return r;
-    if (A->kind == OP_DIAG_LIN && X->dtype == LK_F64) {
-        r.kind = ROWOP_LIN; r.d0 = A->d0; r.dstep = A->dstep; r.row0 = A->row0;
-    } else if (A->kind == OP_DIAG) {
-        r.kind = ROWOP_DIAG; r.d = A->dev; r.conj = trans && X->dtype == LK_C128;
-    }
-    return r;
+    return A->rowop(trans, X->dtype);
 }
 
 constexpr int SEG_LOOKAHEAD = 24;
