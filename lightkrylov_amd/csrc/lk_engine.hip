@@ -1394,28 +1394,79 @@ void resident_maybe_rearm(lk_context_t c) {
 int dgs_resident_launch(lk_basis_t Bx, int k, double *y, double *out, int rs, bool normalize, double tol_scale, double tol_break, int *stop_out,
                         int c0 = 0);
 
+// ---- what the asynchronous batches share: the result slot of a step and the protocol around the enqueue loop ------------------------------
+// The slot of one Gram-Schmidt step against k columns: three sections of rs doubles, h1 | h2 | ||y''||^2.  Each section holds k
+// coefficients and the squared norm behind them; the single launch leaves its status word one double behind the norm of the third.
+// T = const double: a pinned mirror the host reads; T = double: device memory, addresses only.
+template <class T> struct StepSlotT {
+    T *p;
+    int rs, k, ED;
+    T *h1() const { return p; }
+    T *h2() const { return p + rs; }
+    T *nrm2() const { return p + 2 * (size_t)rs + (size_t)k * ED; }
+    double status() const { return nrm2()[1]; }
+    double h(int i) const { return h1()[i] + h2()[i]; }                           // gram_schmidt.fypp:49
+};
+using StepSlot = StepSlotT<const double>;
+using StepSlotDev = StepSlotT<double>;
+// slot number -> address, in a buffer of slots of RED_SECTIONS sections each
+template <class T> inline T *slot_of(T *base, int64_t index, int rs) { return base + (size_t)index * RED_SECTIONS * rs; }
+// lz_red: four sections per Lanczos step, (dot | its finished coefficient) of the two local orthogonalisations; step `s` of the batch, pass `i`
+template <class T> inline T *lz_pass(T *base, int s, int i) { return base + ((size_t)s * 4 + 2 * i) * RED_SECTION; }
+// the real-valued entry of a matrix of either kind
+inline void set_real(double *at, int ED, double v) { at[0] = v; if (ED == 2) at[1] = 0.0; }
+
+// The protocol of an asynchronous batch.  While armed, every launch on the context carries the guard (the device stop flag and the
+// number of the step it belongs to) and, with `sweeps_only`, only the sweeps, the operator and the collectives carry profiling events.
+// The flags are assigned HERE and nowhere else: the destructor takes them down on every way out, so no later plain kernel can see a
+// stop flag that a batch left raised.  The guard must be down wherever foreign code or an entry of the ABI runs: finish() disarms before
+// it collects, and lk_arnoldi_segments disarms around its deliveries.
+class BatchScope {
+    lk_context_t c;
+    bool sweeps_only;
+public:
+    BatchScope(lk_context_t c_, bool sweeps_only_) : c(c_), sweeps_only(sweeps_only_) { arm(); }
+    ~BatchScope() { disarm(); }
+    BatchScope(const BatchScope &) = delete;
+    BatchScope &operator=(const BatchScope &) = delete;
+    void arm() { c->guard_on = true; c->prof_sweeps_only = sweeps_only; }
+    void disarm() { c->guard_on = false; c->guard_step = 0; c->prof_sweeps_only = false; }
+    int begin() { HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream)); return LK_OK; }   // the stop flag of the last batch goes
+    void at(int seq) { c->guard_step = seq; }        // the launches that follow belong to step `seq` (> 0, ascending)
+    // behind the slot copies the caller has enqueued: the stop flag to the host, ONE synchronisation, the profiling records; *stop = the
+    // step that raised the flag, or 0
+    int finish(int *stop) {
+        disarm();
+        HIPCHK(hipMemcpyAsync(c->stop_host, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->prof) prof_collect(c);
+        *stop = *c->stop_host;
+        return LK_OK;
+    }
+};
+
 // One Gram-Schmidt step + normalise of an ASYNCHRONOUS batch (lk_arnoldi / lk_lanczos / lk_bidiag): results into the step slot, the
 // normalise skipped below tol_scale, the device stop flag raised below tol_break.  A cache-resident panel takes the single launch
 // (lk_resident.hip.h); a launch that gives up raises the stop flag and leaves status 1 in the slot -- resident_status() below.
 int dgs_step_async(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *slot, int rs, double tol_scale, double tol_break, int c0 = 0) {
     lk_context_t c = Bx->ctx;
-    const int ED = Bx->ed();
     if (resident_applies(Bx, k)) return dgs_resident_launch(Bx, k, By->col(jy), slot, rs, true, tol_scale, tol_break, c->stop_dev, c0);
     resident_note_fallback(Bx, k);
     LKCHK(dgs_device(Bx, k, By->col(jy), true, slot, rs, c0));
-    return scal_launch(By, jy, 1.0, 0.0, slot + 2 * rs + (size_t)k * ED, tol_scale, c->stop_dev, tol_break);
+    return scal_launch(By, jy, 1.0, 0.0, StepSlotDev{slot, rs, k, Bx->ed()}.nrm2(), tol_scale, c->stop_dev, tol_break);
 }
-// host side of a finished batch: did the step that used `slot` give up (1: redo it on the three-sweep schedule; the context has been
-// switched over) or fail (error)?  0 = it ran, or it never was a single launch.
-int resident_status(lk_basis_t Bx, int k, const double *slot_host, int rs, int *redo) {
+// host side of a finished batch, the only decode of the status word for the ASYNCHRONOUS batches (lk_dgs keeps the synchronous copy in
+// dgs_generic, which goes on to the three sweeps in the same call): did the step that used `slot` give up (1: redo it on the three-sweep
+// schedule; the context has been switched over) or fail (error, its text opened by `entry`)?  0 = it ran, or it never was a single launch.
+int resident_status(lk_basis_t Bx, const StepSlot &slot, int *redo, const char *entry = "") {
     *redo = 0;
-    if (!resident_applies(Bx, k)) return LK_OK;
-    const double status = slot_host[2 * (size_t)rs + (size_t)k * Bx->ed() + 1];
+    if (!resident_applies(Bx, slot.k)) return LK_OK;
+    const double status = slot.status();
     if (status == 1.0) {
         LKCHK(resident_recover(Bx->ctx));
         *redo = 1;
     } else if (status != 0.0) {
-        return fail(LK_ERR_HIP, "the single-launch Gram-Schmidt step failed after its first phase (status %g)", status);
+        return fail(LK_ERR_HIP, "%sthe single-launch Gram-Schmidt step failed after its first phase (status %g)", entry, status);
     }
     return LK_OK;
 }
@@ -2427,7 +2478,6 @@ static int dgs_generic(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *h, d
     ProfScope ps(c, "dgs", dgs_bytes, false, !single);
     if (k <= KMAX_WIDE) {
         const int rs = red_stride(k);
-        const int last = two_pass ? 2 : 1;
         if (single) {
             // the whole step -- both passes and the normalise -- as ONE persistent launch (lk_resident.hip.h)
             c->span_first = nullptr;
@@ -2439,8 +2489,8 @@ static int dgs_generic(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *h, d
                 c->prof_pending.push_back(span);
             }
             LKCHK(fetch(c, 0, 3, rs));
-            const double status = c->red_host[2 * rs + (size_t)k * ED + 1];
-            if (status == 1.0) {            // gave up before touching y (the chip is shared with another persistent kernel)
+            const double status = StepSlot{c->red_host, rs, k, ED}.status();
+            if (status == 1.0) {         // gave up before touching y (the chip is shared with another persistent kernel)
                 LKCHK(resident_recover(c));
                 resident_note_fallback(Bx, k);
                 single = false;
@@ -2450,17 +2500,20 @@ static int dgs_generic(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *h, d
         }
         if (!single) {
             LKCHK(dgs_device(Bx, k, y, two_pass));
-            if (flags & LK_DGS_NORMALIZE)
-                LKCHK(scal_launch(By, jy, 1.0, 0.0, c->red + last * rs + (size_t)k * ED, ATOL_DP));
+            if (flags & LK_DGS_NORMALIZE) {      // the norm of what the last pass left: section 3, or section 2 of the one-pass step
+                const StepSlotDev out{c->red, rs, k, ED};
+                LKCHK(scal_launch(By, jy, 1.0, 0.0, two_pass ? out.nrm2() : out.h2() + (size_t)k * ED, ATOL_DP));
+            }
             ps.end();
             LKCHK(fetch(c, 0, 3, rs));
         }
-        const double *r0 = c->red_host, *r1 = c->red_host + rs, *r2 = c->red_host + 2 * rs;
+        const StepSlot res{c->red_host, rs, k, ED};
+        const double *r0 = res.h1(), *r1 = res.h2();
         if (h)
             for (int i = 0; i < k * ED; ++i) h[i] = two_pass ? (r0[i] + r1[i]) : r0[i];   // gram_schmidt.fypp:49
         n0 = r0[k * ED];
         n1 = r1[k * ED];
-        n2 = two_pass ? r2[k * ED] : n1;
+        n2 = two_pass ? *res.nrm2() : n1;
     } else if (k <= 4 * KMAX_WIDE) {
         // very wide basis, up to four column panels of KMAX_WIDE: everything stays on the device, ONE copy + synchronisation.
         //   sweep 1 : h1_p = X_p^H y for every panel                                   (k columns)
@@ -2735,6 +2788,17 @@ int lk_set_halo_exchange(lk_context_t c, lk_halo_fn fn, void *user) {
 }
 
 // ---- Arnoldi -----------------------------------------------------------------------------------------
+// H(k+1, k) behind step k, whose y'' has the norm beta (normalised on the device unless beta < atol_dp).  *stop = 1: the loop exits (info set).
+static int arnoldi_close_column(lk_basis_t X, double *Hk, int k, double beta, double tol, int *info, int *stop) {
+    double *sub = Hk + (size_t)k * X->ed();
+    set_real(sub, X->ed(), 0.0);
+    // qr_no_pivoting, colinear column: R(1,1) = 0, rand, re-normalise   qr.fypp:146-162
+    if (beta < ATOL_DP) LKCHK(lk_vec_rand(X, k, 0x5EEDull + (uint64_t)k, X->ctx->row0, 1));
+    else sub[0] = beta;
+    if (std::fabs(sub[0]) < tol) { *info = k; *stop = 1; }                         // arnoldi.fypp:58-71
+    return LK_OK;
+}
+
 // One step on the host-synchronous schedule (one round trip per step): used for k > KMAX_FUSED and with
 // async_arnoldi = 0.  Returns through *stop: 0 continue, 1 loop must exit (info set).
 static int arnoldi_step_sync(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int k, double tol, int trans, std::vector<double> &h,
@@ -2747,20 +2811,7 @@ static int arnoldi_step_sync(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh,
     LKCHK(lk_dgs(X, k, X, k, h.data(), norms, LK_DGS_NORMALIZE, &dinfo));          // arnoldi.fypp:50-55
     double *Hk = H + (size_t)(k - 1) * ldh * ED;
     memcpy(Hk, h.data(), (size_t)k * ED * sizeof(double));
-    const double beta = norms[2];
-    Hk[(size_t)k * ED] = 0.0;
-    if (ED == 2) Hk[(size_t)k * ED + 1] = 0.0;
-    if (beta < ATOL_DP) {
-        // qr_no_pivoting, colinear column: R(1,1) = 0, rand, re-normalise   qr.fypp:146-162
-        LKCHK(lk_vec_rand(X, k, 0x5EEDull + (uint64_t)k, X->ctx->row0, 1));
-    } else {
-        Hk[(size_t)k * ED] = beta;
-    }
-    if (std::fabs(Hk[(size_t)k * ED]) < tol) {                                     // arnoldi.fypp:58-71
-        *info = k;
-        *stop = 1;
-    }
-    return LK_OK;
+    return arnoldi_close_column(X, Hk, k, norms[2], tol, info, stop);
 }
 
 // per-step result slots of an asynchronous batch: nsteps x RED_SECTIONS sections of `stride` doubles (red_stride(last step))
@@ -2807,20 +2858,20 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->seg_events.push_back(e);
     }
-    HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
+    BatchScope batch(c, true);
+    LKCHK(batch.begin());
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;
     const int ED = X->ed();
     const size_t slot_doubles = (size_t)RED_SECTIONS * rs;
     int enq = k0;                                    // next step to enqueue
     int si = 0, seg_first = k0;                      // next segment to close, first step of it
-    auto enqueue_until = [&](int kto) -> int {
-        c->guard_on = true;
-        c->prof_sweeps_only = true;
+    auto enqueue_until = [&](int kto) -> int {       // (armed on entry, down on return: the deliveries between two calls run the caller's code)
+        batch.arm();
         int rc = LK_OK;
         for (; enq <= kto && rc == LK_OK; ++enq) {
             const int k = enq;
-            c->guard_step = k;
-            double *slot = c->step_red + (size_t)(k - k0) * slot_doubles;
+            batch.at(k);
+            double *slot = slot_of(c->step_red.get(), k - k0, rs);
             const bool single = resident_applies(X, k);
             // diagonal operator on the three-sweep schedule: no operator kernel, the sweeps form y = D x_k from column k-1 themselves and
             // sweep 3 writes y'' into column k (y never exists in memory).  The single launch still takes a materialised y.
@@ -2842,7 +2893,7 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
                 span.bytes = (double)X->n * ED * 8.0 * (rop.kind == ROWOP_NONE ? 3.0 * k + 5.0 : 3.0 * k + 1.0 + (rop.kind == ROWOP_DIAG ? 3.0 : 0.0));
                 c->prof_pending.push_back(span);
             }
-            if (!single) rc = scal_launch(X, k, 1.0, 0.0, slot + 2 * rs + (size_t)k * ED, ATOL_DP, c->stop_dev, tol_break);
+            if (!single) rc = scal_launch(X, k, 1.0, 0.0, StepSlotDev{slot, rs, k, ED}.nrm2(), ATOL_DP, c->stop_dev, tol_break);
             if (rc == LK_OK && si < nseg && k == seg_last[si]) {
                 // close a segment: its slots and the stop flag as it stands now travel to the host behind this step
                 const size_t off = (size_t)(seg_first - k0) * slot_doubles;
@@ -2855,9 +2906,7 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
                 ++si;
             }
         }
-        c->guard_on = false;
-        c->guard_step = 0;
-        c->prof_sweeps_only = false;
+        batch.disarm();
         return rc;
     };
     *delivered_to = k0 - 1;
@@ -2882,18 +2931,14 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
         HIPCHK(hipMemcpyAsync(c->step_red_host + off, c->step_red + off, (size_t)(klast - seg_first + 1) * slot_doubles * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->stop_host, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->prof) prof_collect(c);
-    const int stop_step = *c->stop_host;
+    int stop_step = 0;
+    LKCHK(batch.finish(&stop_step));
     *done = stop_step ? stop_step : klast;
-    if (*cancelled && stop_step && resident_applies(X, stop_step)) {
+    if (*cancelled && stop_step) {
         // a look-ahead step beyond the delivered ones stopped the device: the caller reads no slot of a cancelled batch, but a single launch
         // that gave up there left the abort word raised -- clear it here, or the next launch on this context finds it at entry
-        const double status = c->step_red_host[(size_t)(stop_step - k0) * slot_doubles + 2 * (size_t)rs + (size_t)stop_step * ED + 1];
-        if (status == 1.0) LKCHK(resident_recover(c));
-        else if (status != 0.0)
-            return fail(LK_ERR_HIP, "lk_arnoldi_segments: the single-launch Gram-Schmidt step failed after its first phase (status %g)", status);
+        int redo = 0;
+        LKCHK(resident_status(X, StepSlot{slot_of<const double>(c->step_red_host, stop_step - k0, rs), rs, stop_step, ED}, &redo, "lk_arnoldi_segments: "));
     }
     return LK_OK;
 }
@@ -2909,35 +2954,25 @@ static int lanczos_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
     LKCHK(ensure_step_buffers(c, nsteps, rs));
     LKCHK(c->lz_red.reserve((int64_t)nsteps * 4 * RED_SECTION));
     LKCHK(c->lz_red_host.reserve((int64_t)nsteps * 4 * RED_SECTION));
-    HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
+    BatchScope batch(c, true);
+    LKCHK(batch.begin());
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;     // below it: stop flag AND no scaling (lanczos.fypp:32-36)
-    c->guard_on = true;
-    c->prof_sweeps_only = true;
-    int rc = LK_OK;
-    for (int k = k0; k <= k1 && rc == LK_OK; ++k) {
-        c->guard_step = k;
-        double *slot = c->step_red + (size_t)(k - k0) * RED_SECTIONS * rs;
-        rc = lk_linop_apply(A, LK_OP_N, X, k - 1, X, k);
+    for (int k = k0; k <= k1; ++k) {
+        batch.at(k);
+        LKCHK(lk_linop_apply(A, LK_OP_N, X, k - 1, X, k));
         const int i0 = k > 1 ? k - 1 : 1;
-        for (int i = i0; i <= k && rc == LK_OK; ++i) {                       // lanczos.fypp:57-60
-            double *a = c->lz_red + ((size_t)(k - k0) * 4 + 2 * (i - i0)) * RED_SECTION;
-            rc = sweepm<1>(X, i - 1, 1, X->col(k), nullptr, nullptr, 1, a);
-            if (rc == LK_OK) rc = sweepm<3>(X, i - 1, 1, X->col(k), a, nullptr, 1, a + RED_SECTION);
+        for (int i = i0; i <= k; ++i) {                                      // lanczos.fypp:57-60
+            double *a = lz_pass(c->lz_red.get(), k - k0, i - i0);
+            LKCHK(sweepm<1>(X, i - 1, 1, X->col(k), nullptr, nullptr, 1, a));
+            LKCHK(sweepm<3>(X, i - 1, 1, X->col(k), a, nullptr, 1, a + RED_SECTION));
         }
-        if (rc != LK_OK) break;
-        rc = dgs_step_async(X, k, X, k, slot, rs, tol_break, tol_break);   // :62 (no beta), :29-39
+        LKCHK(dgs_step_async(X, k, X, k, slot_of(c->step_red.get(), k - k0, rs), rs, tol_break, tol_break));   // :62 (no beta), :29-39
     }
-    c->guard_on = false;
-    c->guard_step = 0;
-    c->prof_sweeps_only = false;
-    LKCHK(rc);
     HIPCHK(hipMemcpyAsync(c->step_red_host, c->step_red, (size_t)nsteps * RED_SECTIONS * rs * sizeof(double),
                           hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->lz_red_host, c->lz_red, (size_t)nsteps * 4 * RED_SECTION * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->stop_host, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->prof) prof_collect(c);
-    const int stop_step = *c->stop_host;
+    int stop_step = 0;
+    LKCHK(batch.finish(&stop_step));
     *done = stop_step ? stop_step : k1;
     return LK_OK;
 }
@@ -2960,8 +2995,7 @@ static int lanczos_step_sync(lk_linop_t A, lk_basis_t X, double *T, int64_t ldt,
     LKCHK(lk_dgs(X, k, X, k, nullptr, norms, 0, &dinfo));                                    // :62 (no beta)
     const double beta = norms[2];
     if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
-    Tk[(size_t)k * ED] = beta;                                                               // :29
-    if (ED == 2) Tk[(size_t)k * ED + 1] = 0.0;
+    set_real(Tk + (size_t)k * ED, ED, beta);                                                 // :29
     if (beta < tol) { *info = k; *stop = 1; return LK_OK; }                                  // :32-36 (no scaling)
     const double inv[2] = {1.0 / beta, 0.0};
     return lk_vec_scal(X, k, inv);                                                           // :39
@@ -2997,20 +3031,19 @@ int lk_lanczos(lk_linop_t A, lk_basis_t X, double *T, int64_t ldt, int kstart, i
         double beta = 0.0;
         const int rs = red_stride(kfused);
         int redo = 0;
-        LKCHK(resident_status(X, done, c->step_red_host + (size_t)(done - k) * RED_SECTIONS * rs, rs, &redo));
+        auto slot = [&](int s) { return StepSlot{slot_of<const double>(c->step_red_host, s - k, rs), rs, s, ED}; };
+        LKCHK(resident_status(X, slot(done), &redo));
         const int upto = redo ? done - 1 : done;              // (a single launch that gave up stopped the batch at `done`: that step runs again)
         for (int s = k; s <= upto; ++s) {
-            const double *r2 = c->step_red_host + ((size_t)(s - k) * RED_SECTIONS + 2) * rs;
             const int i0 = s > 1 ? s - 1 : 1;
             double *Ts = T + (size_t)(s - 1) * ldt * ED;
             for (int i = i0; i <= s; ++i) {
-                const double *a = c->lz_red_host + ((size_t)(s - k) * 4 + 2 * (i - i0)) * RED_SECTION;
+                const double *a = lz_pass<const double>(c->lz_red_host, s - k, i - i0);
                 for (int e = 0; e < ED; ++e) Ts[(size_t)(i - 1) * ED + e] = a[e];           // T(i, k)   :58
             }
-            beta = std::sqrt(std::fabs(r2[(size_t)s * ED]));
+            beta = std::sqrt(std::fabs(*slot(s).nrm2()));
             if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
-            Ts[(size_t)s * ED] = beta;                                                      // T(k+1, k) :29
-            if (ED == 2) Ts[(size_t)s * ED + 1] = 0.0;
+            set_real(Ts + (size_t)s * ED, ED, beta);                                        // T(k+1, k) :29
         }
         if (redo) { k = done; continue; }
         if (!stopped_early) { k = done + 1; continue; }                                       // (on to the steps beyond KMAX_WIDE, if any)
@@ -3031,38 +3064,27 @@ static int bidiag_batch_async(lk_linop_t A, lk_basis_t U, lk_basis_t V, int k0, 
     const int nsteps = k1 - k0 + 1;
     const int rs = red_stride(k1);
     LKCHK(ensure_step_buffers(c, 2 * nsteps, rs));
-    HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
+    BatchScope batch(c, true);
+    LKCHK(batch.begin());
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;
-    c->guard_on = true;
-    c->prof_sweeps_only = true;
-    int rc = LK_OK;
-    for (int k = k0; k <= k1 && rc == LK_OK; ++k) {
-        double *sv = c->step_red + (size_t)(2 * (k - k0)) * RED_SECTIONS * rs;
-        double *su = sv + (size_t)RED_SECTIONS * rs;
-        c->guard_step = 2 * k - 1;
-        rc = lk_linop_apply(A, LK_OP_H, U, k - 1, V, k - 1);                                   // :27
-        if (rc != LK_OK) break;
-        if (k > 1) rc = dgs_step_async(V, k - 1, V, k - 1, sv, rs, tol_break, tol_break);     // :30-33, :36-42
+    for (int k = k0; k <= k1; ++k) {
+        double *sv = slot_of(c->step_red.get(), 2 * (k - k0), rs), *su = slot_of(c->step_red.get(), 2 * (k - k0) + 1, rs);
+        batch.at(2 * k - 1);
+        LKCHK(lk_linop_apply(A, LK_OP_H, U, k - 1, V, k - 1));                                 // :27
+        if (k > 1) LKCHK(dgs_step_async(V, k - 1, V, k - 1, sv, rs, tol_break, tol_break));   // :30-33, :36-42
         else {
-            rc = dot_device(V, 0, V, 0, sv + 2 * rs);                                         // ||V(1)||^2 where the DGS would leave it
-            if (rc == LK_OK) rc = scal_launch(V, 0, 1.0, 0.0, sv + 2 * rs, tol_break, c->stop_dev, tol_break);
+            double *nrm2 = StepSlotDev{sv, rs, 0, V->ed()}.nrm2();                            // ||V(1)||^2 where the DGS would leave it
+            LKCHK(dot_device(V, 0, V, 0, nrm2));
+            LKCHK(scal_launch(V, 0, 1.0, 0.0, nrm2, tol_break, c->stop_dev, tol_break));
         }
-        if (rc != LK_OK) break;
-        c->guard_step = 2 * k;
-        rc = lk_linop_apply(A, LK_OP_N, V, k - 1, U, k);                                       // :45
-        if (rc != LK_OK) break;
-        rc = dgs_step_async(U, k, U, k, su, rs, tol_break, tol_break);                        // :48-49, :52-58
+        batch.at(2 * k);
+        LKCHK(lk_linop_apply(A, LK_OP_N, V, k - 1, U, k));                                     // :45
+        LKCHK(dgs_step_async(U, k, U, k, su, rs, tol_break, tol_break));                      // :48-49, :52-58
     }
-    c->guard_on = false;
-    c->guard_step = 0;
-    c->prof_sweeps_only = false;
-    LKCHK(rc);
     HIPCHK(hipMemcpyAsync(c->step_red_host, c->step_red, (size_t)2 * nsteps * RED_SECTIONS * rs * sizeof(double),
                           hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->stop_host, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->prof) prof_collect(c);
-    const int stop_half = *c->stop_host;
+    int stop_half = 0;
+    LKCHK(batch.finish(&stop_half));
     *done_half = stop_half ? stop_half : 2 * k1;
     return LK_OK;
 }
@@ -3091,25 +3113,23 @@ int lk_bidiag(lk_linop_t A, lk_basis_t U, lk_basis_t V, double *B, int64_t ldb, 
         stopped_early = *c->stop_host != 0;
         const int rs = red_stride(kfused);
         int redo = 0;
+        // half step hs = 2k - 1 (right) orthogonalised V(k) against k - 1 columns, hs = 2k (left) U(k+1) against k: hs / 2 either way
+        auto slot = [&](int hs) { return StepSlot{slot_of<const double>(c->step_red_host, hs - (2 * ks - 1), rs), rs, hs / 2, ED}; };
         if (stopped_early) {
             // the half step the batch stopped at: did its single-launch Gram-Schmidt step give up?  Then the whole step runs again
             // (both halves: recomputing the right half from the untouched U(k) gives the same bits) on the three-sweep schedule.
-            const int kq = (done_half + 1) / 2;
             const bool right = done_half & 1;
-            const double *slot = c->step_red_host + (size_t)(done_half - (2 * ks - 1)) * RED_SECTIONS * rs;
-            if (!(right && kq == 1)) LKCHK(resident_status(right ? V : U, right ? kq - 1 : kq, slot, rs, &redo));
+            if (done_half != 1) LKCHK(resident_status(right ? V : U, slot(done_half), &redo));      // (half step 1 is a norm alone)
         }
         const int upto = redo ? done_half - 1 : done_half;
         for (int hs = 2 * ks - 1; hs <= upto; ++hs) {
             const int k = (hs + 1) / 2;
             const bool right = hs & 1;
-            const double *r2 = c->step_red_host + ((size_t)(hs - (2 * ks - 1)) * RED_SECTIONS + 2) * rs;
-            const double nrm = std::sqrt(std::fabs(r2[(size_t)(right ? k - 1 : k) * ED]));
+            const double nrm = std::sqrt(std::fabs(*slot(hs).nrm2()));
             if (nrm != nrm) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
             double *Bk = B + (size_t)(k - 1) * ldb * ED;
             const size_t row = right ? (size_t)(k - 1) : (size_t)k;                           // B(k, k) = alpha ; B(k+1, k) = beta
-            Bk[row * ED] = nrm;
-            if (ED == 2) Bk[row * ED + 1] = 0.0;
+            set_real(Bk + row * ED, ED, nrm);
         }
         if (!redo) break;
         ks = (done_half + 1) / 2;
@@ -3126,8 +3146,7 @@ int lk_bidiag(lk_linop_t A, lk_basis_t U, lk_basis_t V, double *B, int64_t ldb, 
         else LKCHK(lk_vec_norm(V, 0, &norms[2]));
         const double alpha = norms[2];                                                     // :36
         if (alpha != alpha) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
-        Bk[(size_t)(k - 1) * ED] = alpha;
-        if (ED == 2) Bk[(size_t)(k - 1) * ED + 1] = 0.0;
+        set_real(Bk + (size_t)(k - 1) * ED, ED, alpha);
         if (!(std::fabs(alpha) > tol)) { *info = k; return LK_OK; }                        // :37-42
         const double ia[2] = {1.0 / alpha, 0.0};
         LKCHK(lk_vec_scal(V, k - 1, ia));
@@ -3135,8 +3154,7 @@ int lk_bidiag(lk_linop_t A, lk_basis_t U, lk_basis_t V, double *B, int64_t ldb, 
         LKCHK(lk_dgs(U, k, U, k, nullptr, norms, 0, &dinfo));                              // :48-49
         const double beta = norms[2];                                                      // :52
         if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
-        Bk[(size_t)k * ED] = beta;
-        if (ED == 2) Bk[(size_t)k * ED + 1] = 0.0;
+        set_real(Bk + (size_t)k * ED, ED, beta);
         if (!(std::fabs(beta) > tol)) { *info = k; return LK_OK; }                         // :53-58
         const double ib[2] = {1.0 / beta, 0.0};
         LKCHK(lk_vec_scal(U, k, ib));
@@ -3186,34 +3204,16 @@ static int arnoldi_impl(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int 
         int redo = 0;                                            // step whose single-launch Gram-Schmidt gave up (the batch stopped there)
         auto fill = [&](int sa, int sb, int *stop_out) -> int {
             for (int s = sa; s <= sb; ++s) {
-                const double *slot = c->step_red_host + (size_t)(s - kb) * RED_SECTIONS * rs;
-                const double *r0 = slot, *r1 = slot + rs, *r2 = slot + 2 * rs;
-                if (resident_applies(X, s)) {
-                    const double status = r2[(size_t)s * ED + 1];
-                    if (status == 1.0) {                          // y untouched: this step runs again on the three-sweep schedule
-                        LKCHK(resident_recover(c));
-                        redo = s;
-                        return LK_OK;
-                    }
-                    if (status != 0.0) return fail(LK_ERR_HIP, "lk_arnoldi: the single-launch Gram-Schmidt step failed after its first phase (status %g)", status);
-                }
+                const StepSlot slot{slot_of<const double>(c->step_red_host, s - kb, rs), rs, s, ED};
+                int gave_up = 0;
+                LKCHK(resident_status(X, slot, &gave_up, "lk_arnoldi: "));
+                if (gave_up) { redo = s; return LK_OK; }         // y untouched: this step runs again on the three-sweep schedule
                 double *Hk = H + (size_t)(s - 1) * ldh * ED;
-                for (int i = 0; i < s * ED; ++i) Hk[i] = r0[i] + r1[i];                 // gram_schmidt.fypp:49
-                const double beta = std::sqrt(std::fabs(r2[s * ED]));
+                for (int i = 0; i < s * ED; ++i) Hk[i] = slot.h(i);
+                const double beta = std::sqrt(std::fabs(*slot.nrm2()));
                 if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
-                Hk[(size_t)s * ED] = 0.0;
-                if (ED == 2) Hk[(size_t)s * ED + 1] = 0.0;
-                if (beta < ATOL_DP) {
-                    // colinear column (the device left y'' unnormalised and stopped): R(1,1) = 0, rand, re-normalise  qr.fypp:146-162
-                    LKCHK(lk_vec_rand(X, s, 0x5EEDull + (uint64_t)s, c->row0, 1));
-                } else {
-                    Hk[(size_t)s * ED] = beta;
-                }
-                if (std::fabs(Hk[(size_t)s * ED]) < tol) {                              // arnoldi.fypp:58-71
-                    *info = s;
-                    *stop_out = 1;
-                    return LK_OK;
-                }
+                LKCHK(arnoldi_close_column(X, Hk, s, beta, tol, info, stop_out));   // (below atol_dp the device left y'' unnormalised and stopped)
+                if (*stop_out) return LK_OK;
             }
             return LK_OK;
         };
@@ -3292,8 +3292,7 @@ static int qr_columns_sync(lk_basis_t X, int c0, int p, int jbeg, bool have_firs
         if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");           // :137-143
         if (std::fabs(beta) < tol) {                                                       // colinear column  :146-162
             if (!*flag) { *flag = true; *info = j + 1; }
-            Rj[(size_t)j * ED] = 0.0;
-            if (ED == 2) Rj[(size_t)j * ED + 1] = 0.0;
+            set_real(Rj + (size_t)j * ED, ED, 0.0);
             LKCHK(lk_vec_rand(X, c0 + j, QR_SEED + (uint64_t)(c0 + j) + 1, c->row0, 0));
             if (j > 0) {
                 lk_basis_s Qv = basis_view(X, c0, j);
@@ -3303,8 +3302,7 @@ static int qr_columns_sync(lk_basis_t X, int c0, int p, int jbeg, bool have_firs
             LKCHK(lk_vec_norm(X, c0 + j, &beta));
             scaled = false;
         } else {
-            Rj[(size_t)j * ED] = beta;
-            if (ED == 2) Rj[(size_t)j * ED + 1] = 0.0;
+            set_real(Rj + (size_t)j * ED, ED, beta);
         }
         if (!scaled) {
             const double inv[2] = {1.0 / beta, 0.0};
@@ -3334,7 +3332,6 @@ int lk_qr(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, double tol, int *
 static int arnoldi_block_batch(lk_linop_t A, lk_basis_t X, int p, int k0, int k1, double tol, int trans, std::vector<int64_t> &blk_off,
                                int64_t *qr_off) {
     lk_context_t c = X->ctx;
-    const int ED = X->ed();
     const int nsteps = k1 - k0 + 1;
     const int rs = RED_SECTION;                                          // the block's columns see at most p - 1 <= 31 basis columns
     blk_off.assign(nsteps + 1, 0);
@@ -3342,38 +3339,31 @@ static int arnoldi_block_batch(lk_linop_t A, lk_basis_t X, int p, int k0, int k1
     *qr_off = blk_off[nsteps];
     const int64_t total = *qr_off + (int64_t)nsteps * p * RED_SECTIONS * rs;
     LKCHK(ensure_block_buffers(c, total));
-    HIPCHK(hipMemsetAsync(c->stop_dev, 0, sizeof(int), c->stream));
+    BatchScope batch(c, false);                                          // (every kernel of a block step keeps its profiling events)
+    LKCHK(batch.begin());
     const double tol_break = tol > ATOL_DP ? tol : ATOL_DP;
-    c->guard_on = true;
-    int rc = LK_OK;
-    for (int k = k0; k <= k1 && rc == LK_OK; ++k) {
+    for (int k = k0; k <= k1; ++k) {
         const int kpm = (k - 1) * p, kp = k * p;
         const int seq0 = (k - k0) * (p + 1) + 1;
-        c->guard_step = seq0;
-        for (int i = 0; i < p && rc == LK_OK; ++i) rc = lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, kpm + i, X, kp + i);   // :39-47
-        if (rc != LK_OK) break;
-        rc = dgs_block_walk(X, kp, X, kp, p, c->blk_red + blk_off[k - k0], nullptr, nullptr, nullptr, 0);                 // :50-51
-        for (int j = 0; j < p && rc == LK_OK; ++j) {                                                                    // :55
-            c->guard_step = seq0 + 1 + j;
-            double *slot = c->blk_red + *qr_off + ((int64_t)(k - k0) * p + j) * RED_SECTIONS * rs;
+        batch.at(seq0);
+        for (int i = 0; i < p; ++i) LKCHK(lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, kpm + i, X, kp + i));           // :39-47
+        LKCHK(dgs_block_walk(X, kp, X, kp, p, c->blk_red + blk_off[k - k0], nullptr, nullptr, nullptr, 0));              // :50-51
+        for (int j = 0; j < p; ++j) {                                                                                   // :55
+            batch.at(seq0 + 1 + j);
+            double *slot = slot_of(c->blk_red + *qr_off, (int64_t)(k - k0) * p + j, rs);
             if (j > 0) {
                 lk_basis_s Qv = basis_view(X, kp, j);
-                rc = dgs_step_async(&Qv, j, X, kp + j, slot, rs, ATOL_DP, tol_break);
+                LKCHK(dgs_step_async(&Qv, j, X, kp + j, slot, rs, ATOL_DP, tol_break));
             } else {
-                rc = dot_device(X, kp, X, kp, slot + 2 * rs);
-                if (rc == LK_OK) rc = scal_launch(X, kp, 1.0, 0.0, slot + 2 * rs, ATOL_DP, c->stop_dev, tol_break);
+                double *nrm2 = StepSlotDev{slot, rs, 0, X->ed()}.nrm2();
+                LKCHK(dot_device(X, kp, X, kp, nrm2));
+                LKCHK(scal_launch(X, kp, 1.0, 0.0, nrm2, ATOL_DP, c->stop_dev, tol_break));
             }
         }
     }
-    c->guard_on = false;
-    c->guard_step = 0;
-    LKCHK(rc);
     HIPCHK(hipMemcpyAsync(c->blk_red_host, c->blk_red, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->stop_host, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->prof) prof_collect(c);
-    (void)ED;
-    return LK_OK;
+    int stop_seq = 0;
+    return batch.finish(&stop_seq);                                      // (the caller reads *c->stop_host)
 }
 
 int lk_arnoldi_block(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int blksize, int kstart, int kend, double tol, int trans, int *info) {
@@ -3442,17 +3432,17 @@ int lk_arnoldi_block(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int blk
             double beta_last = 0.0;
             bool redo_last = false;
             for (int j = 0; j <= jlast; ++j) {
-                const double *slot = host + qr_off + ((int64_t)(s - k0) * p + j) * RED_SECTIONS * rs;
+                const StepSlot slot{slot_of(host + qr_off, (int64_t)(s - k0) * p + j, rs), rs, j, ED};
                 double *Rj = Hat(kp, kpm + j);
                 for (int i = 0; i < p * ED; ++i) Rj[i] = 0.0;
                 if (j > 0) {
                     lk_basis_s Qv = basis_view(X, kp, j);
                     int redo = 0;
-                    LKCHK(resident_status(&Qv, j, slot, rs, &redo));
+                    LKCHK(resident_status(&Qv, slot, &redo));
                     if (redo) { redo_last = true; break; }                  // (only the column the batch stopped at can have given up)
-                    for (int i = 0; i < j * ED; ++i) Rj[i] = slot[i] + slot[rs + i];                                  // gram_schmidt.fypp:49
+                    for (int i = 0; i < j * ED; ++i) Rj[i] = slot.h(i);
                 }
-                const double beta = std::sqrt(std::fabs(slot[2 * rs + (size_t)j * ED]));
+                const double beta = std::sqrt(std::fabs(*slot.nrm2()));
                 if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");
                 Rj[(size_t)j * ED] = beta;
                 beta_last = beta;
