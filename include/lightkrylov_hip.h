@@ -123,7 +123,7 @@ int lk_set_allgather(lk_context_t ctx, lk_allgather_fn fn, void *user);
 /* row block owned by this rank: global rows [row0, row0 + n_local) of n_global; only used
  * so that counter-based rand fills are identical for every partition. */
 int lk_set_partition(lk_context_t ctx, int64_t row0, int64_t n_global);
-/* Tuning keys (integers; 29 of them -- round 6 removed every key whose other setting was measured slower and never defaulted, the
+/* Tuning keys (integers; 30 of them -- round 6 removed every key whose other setting was measured slower and never defaulted, the
  * record of those A/Bs is docs/TUNING_LOG.md).  None changes a result beyond rounding; the ones marked [bits] change no result bit.
  *   schedule      "async_arnoldi" (1: lk_arnoldi / lk_arnoldi_block enqueue all steps behind a device-side breakdown flag, one host
  *                 synchronisation per call; 0: one round trip per step; lk_lanczos / lk_bidiag always enqueue and do not read the key)
@@ -137,7 +137,10 @@ int lk_set_partition(lk_context_t ctx, int64_t row0, int64_t n_global);
  *   sweeps        "recompute_update" (1: sweep 2 keeps y' in registers, sweep 3 re-forms it: y' never goes to HBM; 0: y' stored, sweep 3
  *                 on the streaming update kernel -- another summation order over the columns, so y'' changes by rounding); "store_policy"
  *                 (cache policy of the sweeps' 16-byte y store: 0 plain, 1 nt, 2 sc1 = write-through [default], 3 sc0 sc1) and
- *                 "store_split" [bits]; "dot_colwise" (1: sweep 1 / innerprod one column at a time, panel_dot_cw; 0: all columns per
+ *                 "store_split" [bits]; "stream_two" (sweep 3 of the recomputing schedule against at most 128 columns one column at a time,
+ *                 y in registers and y'' stored once per run of rows, in sweep 2's summation order: y'' bit for bit as the tile kernel
+ *                 writes it, its norm summed over another row-to-lane mapping and so equal by rounding only; 1 = always, 2 = the real
+ *                 kind on long panels, 0 = the tile kernel); "dot_colwise" (1: sweep 1 / innerprod one column at a time, panel_dot_cw; 0: all columns per
  *                 tile) with "cw_u" (16-byte loads per lane and column: 4, 8, 0 = by size) and "cw_grid_mult"; "grid_mult", "blas1_grid_mult" (blocks per CU: the number of per-block partial sums a dot is assembled from);
  *                 "wide_regs" (update sweeps against 129..384 columns: 2 = register tiles of 32 / 24 columns + the lane split on 24-column
  *                 groups, 1 = the first only, 0 = lane split on 16-column groups) and "wide_s3" (1: sweep 3 of a lane-split step holds both

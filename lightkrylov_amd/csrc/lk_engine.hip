@@ -88,7 +88,8 @@ struct lk_context_s {
     int gemm_mfma_min = 0;     // ... for at least this many output columns (0: 5 real / 9 complex, from profiles/r03_lincomb_scan.txt);
                                // narrower products stream X through the VALU kernel with 1 / 2 / 4 / 8 accumulators per lane
     int gemm_store_policy = 2; // cache policy of the product's output stores (as store_policy: 2 = sc1 write-through)
-    int stream_two = 0;        // sweep 3 with two coefficient sets: barrier-free streaming kernel instead of the LDS/barrier one
+    int stream_two = 2;        // sweep 3 with two coefficient sets one column at a time (panel_update<.., true>: y'' bit for bit as the tile kernel's, the
+                               // norm by rounding) instead of on the tile kernel: 1 = every narrow base (<= 128 columns), 2 = by size, 0 = never
     int recompute_update = 1;  // two-pass DGS: sweep 2 does not store y'; sweep 3 re-forms it (3k+4 instead of 3k+5 columns)
     int store_policy = 2;      // cache policy of the sweeps' y store: 0 plain, 1 nt, 2 sc1 (write-through; +2% on sweep 3), 3 sc0 sc1
     int store_split = 0;       // every wave of the column split stores a lane slice instead of the wc == 0 wave
@@ -442,8 +443,12 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
     // read nor (sweeps 1, 2) written: k | k | k+1 columns, plus the column of d an explicit diagonal reads
     const double bytes = rop.kind != ROWOP_NONE ? (double)n * ED * 8.0 * (k + (MODE == 4 ? 1 : 0) + (rop.kind == ROWOP_DIAG ? 1 : 0))
                                                 : (double)n * ED * 8.0 * (k + 1 + (UPDATE ? 1 : 0));
-    if (rop.kind != ROWOP_NONE && (MODE == 3 || (MODE == 4 && c->stream_two && G == 1) || !rowop_fusable<CPLX, KC>))
+    if (rop.kind != ROWOP_NONE && (MODE == 3 || !rowop_fusable<CPLX, KC>))
         return fail(LK_ERR_INVALID, "internal: this sweep takes no row operator");
+    // "stream_two": the two-coefficient sweep one column at a time (panel_update<.., true>) in sweep 2's summation order.  Bases of at most
+    // KMAX_FUSED columns only: the wide register tiles (SC = 1, G = 1 too), the lane-split and the G > 1 shapes keep the tile kernel.  2 = by size: the real kind on panels long enough to give every CU several runs
+    const bool col_two = MODE == 4 && SC == 1 && G == 1 && k <= KMAX_FUSED &&
+                         (c->stream_two == 1 || (c->stream_two == 2 && !CPLX && n >= (int64_t)NW * 64 * K<CPLX>::ROWS * update_two_u<NW> * c->num_cu * 8));
     int nblocks = s.grid;
     if (MODE == 1 && c->dot_colwise) {
         // sweep 1 one column at a time (panel_dot_cw): y in registers, U KiB of contiguous rows per wave and column
@@ -479,7 +484,26 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
         // the sweep's two HIP events ride on the kernel's own dispatch (start / stop timestamps of the launch itself), not on
         // separate stream markers: six markers per Arnoldi step cost 3-4 % of a launch-bound factorisation (n = 10^6 complex)
         ProfScope ps(c, MODE == 1 ? "dgs_sweep1" : (MODE == 2 ? "dgs_sweep2" : "dgs_sweep3"), bytes, c->prof_ext);
-        if ((MODE == 3 && c->stream_update) || (MODE == 4 && c->stream_two && G == 1)) {
+        if (col_two) {
+            // a grid rule of its own (panel_dot_cw's): runs of U block-wide accesses, one block per CU (the run's registers fill the CU's
+            // share of the file), and every block the same number of runs
+            const int64_t run_rows = (int64_t)NW * 64 * K<CPLX>::ROWS * update_two_u<NW>;
+            int64_t g = (n + run_rows - 1) / run_rows;
+            int64_t cap = (int64_t)c->num_cu;
+            if (cap > MAX_GRID) cap = MAX_GRID;
+            if (g > cap) {
+                const int64_t rounds = (g + cap - 1) / cap;
+                g = (g + rounds - 1) / rounds;
+            }
+            if (g < 1) g = 1;
+            nblocks = (int)g;
+            if (ps.on && ps.ext)
+                hipExtLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, X, ldx,
+                                      k, y, n, hin, hin2, c->partial.get(), (int64_t)MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
+            else
+                hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin, hin2,
+                                   c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
+        } else if (MODE == 3 && c->stream_update) {
             ps.ext = false;
             if (ps.on) (void)hipEventRecord(ps.rec.e0, c->stream);
             const int64_t tile_rows = (int64_t)NW * 64 * K<CPLX>::ROWS;
@@ -490,7 +514,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             if (g < 1) g = 1;
             nblocks = (int)g;
             hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y,
-                               n, hin, hin2, c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard());
+                               n, hin, hin2, c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), 1, k, RowOp{});
         } else {
             const int st = (store ? (1 | (c->store_policy << 1) | (c->store_split ? 8 : 0)) : 0) | (c->xcd_map ? 16 : 0);
             if (ps.on && ps.ext)
@@ -1699,6 +1723,7 @@ int lk_set_tuning(lk_context_t c, const char *key, int value) {
         return LK_OK;
     }
     if (!strcmp(key, "store_split")) { c->store_split = value != 0; return LK_OK; }
+    if (!strcmp(key, "stream_two")) { c->stream_two = value < 0 ? 0 : (value > 2 ? 2 : value); return LK_OK; }
     if (!strcmp(key, "gemm_3m")) { c->gemm_3m = value ? 1 : 0; return LK_OK; }
     if (!strcmp(key, "upd_rs")) { c->upd_rs = value != 0; return LK_OK; }
     if (!strcmp(key, "gram_rs")) { c->gram_rs = value < 0 ? 0 : (value > 16 ? 16 : value); return LK_OK; }
@@ -2839,7 +2864,7 @@ static int ensure_step_buffers(lk_context_t c, int nsteps, int stride) {
 static RowOp fused_rowop(lk_linop_t A, lk_basis_t X, int k, int trans) {
     lk_context_t c = X->ctx;
     RowOp r{};
-    if (!c->fuse_rowop || !c->recompute_update || c->stream_two || A->dtype != X->dtype || A->n != X->n) return r;
+    if (!c->fuse_rowop || !c->recompute_update || A->dtype != X->dtype || A->n != X->n) return r;
     if (X->dtype == LK_C128 && k > KMAX_FUSED) return r;
     return A->rowop(trans, X->dtype);
 }

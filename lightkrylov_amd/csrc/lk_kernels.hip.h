@@ -929,51 +929,149 @@ __global__ __launch_bounds__(NW * 64) void panel_sweep_p(const double *__restric
 // Streaming update y <- y - X(:, :k) * hin with ||y_out||^2: no dots, so nothing has to stay in
 // registers and every wave can walk ALL k columns of its own rows in chunks of KC -- no LDS
 // exchange, no barrier in the loop.  Used for DGS sweep 3 and for linear_combination.
+//
+// TWO (DGS sweep 3 behind a sweep 2 that kept y' in registers; "stream_two"): y'' = (y - X h1) - X h2, ONE COLUMN AT A TIME as
+// panel_dot_cw walks sweep 1.  Sweep 3 accumulates no dots, so it needs no row tile of all k columns on chip: a block keeps its rows
+// of y in registers (U 16-byte accesses per lane = a run of U * NW KiB of contiguous rows per column and block), walks the columns
+// 0 .. k-1 through them and stores y'' once per run, behind the run's last load.  What makes it a partner of the recomputing sweep 2
+// is the ORDER of the sums: per row it adds exactly what panel_sweep<.., TWO> adds with the same (WC, kcw) -- the share `u` of a
+// column group (kcw columns in slot order from zero, the same multiply-add expression), then the groups' shares from zero in the
+// order w = 0, 1, .. of the LDS exchange (WC == 1: the share itself), for both coefficient sets, then yv -= s; yv -= s2 -- so y''
+// comes out bit for bit as the tile kernel writes it.  (The tile kernel's empty register slots and column-less waves add +0 to sums
+// that started from +0 and so are never -0: leaving them out changes no bit.)  ||y''||^2 is summed over another row-to-lane mapping,
+// so the norm differs from the tile kernel's by rounding.  y may be formed from column k-1 by a row operator, as in the other sweeps.
+// KC is no chunk width here; the block shape (NW) selects U: 8 for the 512-thread blocks (y, x, u, u2, s, s2: 192 of 256 registers),
+// 2 for the 1024-thread complex shape (128 registers per lane).
+template <int NW> constexpr int update_two_u = NW > 8 ? 2 : 8;
+
 template <bool CPLX, int KC, int NW, bool TWO>
 __global__ __launch_bounds__(NW * 64) void panel_update(const double *__restrict__ X, int64_t ldx, int k,
                                                          double *__restrict__ y, int64_t n,
                                                          const double *__restrict__ hin,
                                                          const double *__restrict__ hin2,
                                                          double *__restrict__ partial, int64_t pstride, int policy,
-                                                         Guard guard) {
+                                                         Guard guard, int WC, int kcw, RowOp rop) {
     if (stopped(guard)) return;
     constexpr int ROWS = K<CPLX>::ROWS;
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
     constexpr int WROWS = 64 * ROWS;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t tile_rows = (int64_t)NW * WROWS;
-    const int64_t ntiles = (n + tile_rows - 1) / tile_rows;
     const int64_t colstride = ldx * ED;
     double nrm = 0.0;
     __shared__ double red_lds[NW];
 
-    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int64_t r = t * tile_rows + (int64_t)wave * WROWS + (int64_t)lane * ROWS;
-        const bool full = (t + 1) * tile_rows <= n;
-        v2d u = v2d{0.0, 0.0}, u2 = v2d{0.0, 0.0};
-        v2d yv = load_y<CPLX>(y, r, n, full);
-        for (int c0 = 0; c0 < k; c0 += KC) {
-            int nc = k - c0;
-            nc = nc > KC ? KC : nc;
-            v2d xv[KC];
-            load_cols<CPLX, KC>(X + (int64_t)c0 * colstride, colstride, r, n, full, nc, xv);
+    if constexpr (TWO) {
+        constexpr int U = update_two_u<NW>;
+        constexpr int SEG = NW * WROWS;                 // rows one block-wide 16-byte access covers
+        const int64_t run_rows = (int64_t)SEG * U;
+        const int64_t nruns = (n + run_rows - 1) / run_rows;
+        const double *xk = X + (int64_t)(k - 1) * colstride;     // rop: y is formed from column k-1 (x_k) instead of being loaded
+        for (int64_t t = blockIdx.x; t < nruns; t += gridDim.x) {
+            const int64_t r0 = t * run_rows + (int64_t)threadIdx.x * ROWS;
+            const bool full = (t + 1) * run_rows <= n;   // block-uniform
+            v2d yv[U], s[U], s2[U];
+            // the run's y through load_y_op, the block-uniform choices (operator kind, ragged run) taken OUTSIDE the U accesses: left
+            // inside, every access sits behind its own branches and waits for the one before it -- U dependent round trips per run
+            auto take_y = [&](RowOp op, bool f) {
 #pragma unroll
-            for (int jj = 0; jj < KC; ++jj) {
-                if (jj < nc) {
-                    if constexpr (CPLX) u += cmul(xv[jj], v2d{hin[2 * (c0 + jj)], hin[2 * (c0 + jj) + 1]});
-                    else u += xv[jj] * hin[c0 + jj];
-                    if constexpr (TWO) {
-                        if constexpr (CPLX) u2 += cmul(xv[jj], v2d{hin2[2 * (c0 + jj)], hin2[2 * (c0 + jj) + 1]});
-                        else u2 += xv[jj] * hin2[c0 + jj];
+                for (int i = 0; i < U; ++i) yv[i] = load_y_op<CPLX>(op, y, xk, r0 + (int64_t)i * SEG, n, f);
+            };
+            auto take_y_kind = [&](int kind) {
+                RowOp op = rop;
+                op.kind = kind;
+                if (full) take_y(op, true);
+                else take_y(op, false);
+            };
+            if (rop.kind == ROWOP_NONE) take_y_kind(ROWOP_NONE);
+            else if (rop.kind == ROWOP_LIN) take_y_kind(ROWOP_LIN);
+            else take_y_kind(ROWOP_DIAG);
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                s[i] = v2d{0.0, 0.0};
+                s2[i] = v2d{0.0, 0.0};
+            }
+            for (int c0 = 0; c0 < k; c0 += kcw) {       // column group w = c0 / kcw of sweep 2's wave split
+                const int cend = c0 + kcw < k ? c0 + kcw : k;
+                v2d u[U], u2[U];
+#pragma unroll
+                for (int i = 0; i < U; ++i) {
+                    u[i] = v2d{0.0, 0.0};
+                    u2[i] = v2d{0.0, 0.0};
+                }
+                for (int j = c0; j < cend; ++j) {
+                    const double *xc = X + (int64_t)j * colstride;
+                    v2d xv[U];
+                    if (full) {
+#pragma unroll
+                        for (int i = 0; i < U; ++i)
+                            xv[i] = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(xc + (r0 + (int64_t)i * SEG) * ED));
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < U; ++i) xv[i] = load_y<CPLX>(xc, r0 + (int64_t)i * SEG, n, false);
+                    }
+                    // wave-uniform coefficients (scalar loads); the expressions are panel_sweep's, so they contract alike
+                    if constexpr (CPLX) {
+                        const v2d h1 = v2d{hin[2 * j], hin[2 * j + 1]}, h2 = v2d{hin2[2 * j], hin2[2 * j + 1]};
+#pragma unroll
+                        for (int i = 0; i < U; ++i) {
+                            u[i] += cmul(xv[i], h1);
+                            u2[i] += cmul(xv[i], h2);
+                        }
+                    } else {
+                        const v2d h1 = v2d{hin[j], 0.0}, h2 = v2d{hin2[j], 0.0};
+#pragma unroll
+                        for (int i = 0; i < U; ++i) {
+                            u[i] += xv[i] * h1.x;
+                            u2[i] += xv[i] * h2.x;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < U; ++i) {
+                    if (WC > 1) {
+                        s[i] += u[i];
+                        s2[i] += u2[i];
+                    } else {
+                        s[i] = u[i];
+                        s2[i] = u2[i];
                     }
                 }
             }
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                yv[i] -= s[i];
+                yv[i] -= s2[i];      // y'' = (y - X h1) - X h2
+                store_rows<CPLX>(y, r0 + (int64_t)i * SEG, n, full, yv[i], policy);
+                nrm += yv[i].x * yv[i].x + yv[i].y * yv[i].y;
+            }
         }
-        yv -= u;
-        if constexpr (TWO) yv -= u2;      // y'' = (y - X h1) - X h2
-        store_rows<CPLX>(y, r, n, full, yv, policy);
-        nrm += yv.x * yv.x + yv.y * yv.y;
+    } else {
+        // single coefficient set: every wave walks all k columns of its own rows in chunks of KC
+        const int64_t tile_rows = (int64_t)NW * WROWS;
+        const int64_t ntiles = (n + tile_rows - 1) / tile_rows;
+        for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+            const int64_t r = t * tile_rows + (int64_t)wave * WROWS + (int64_t)lane * ROWS;
+            const bool full = (t + 1) * tile_rows <= n;
+            v2d u = v2d{0.0, 0.0};
+            v2d yv = load_y<CPLX>(y, r, n, full);
+            for (int c0 = 0; c0 < k; c0 += KC) {
+                int nc = k - c0;
+                nc = nc > KC ? KC : nc;
+                v2d xv[KC];
+                load_cols<CPLX, KC>(X + (int64_t)c0 * colstride, colstride, r, n, full, nc, xv);
+#pragma unroll
+                for (int jj = 0; jj < KC; ++jj) {
+                    if (jj < nc) {
+                        if constexpr (CPLX) u += cmul(xv[jj], v2d{hin[2 * (c0 + jj)], hin[2 * (c0 + jj) + 1]});
+                        else u += xv[jj] * hin[c0 + jj];
+                    }
+                }
+            }
+            yv -= u;
+            store_rows<CPLX>(y, r, n, full, yv, policy);
+            nrm += yv.x * yv.x + yv.y * yv.y;
+        }
     }
     const double s = wave_sum(nrm);
     if (lane == 0) red_lds[wave] = s;

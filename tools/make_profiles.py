@@ -76,7 +76,8 @@ def traffic_record(sub_fetch, sub_write, shard_of):
     pb = bench_line(os.path.join(src, sub_fetch + ".log")) or {}
     n_local = pb.get("config", {}).get("n_local", 100_000_000)
     m = pb.get("config", {}).get("m", 128)
-    is_sweep = lambda k: "panel_sweep" in k or "panel_dot_cw" in k          # sweep 1 is panel_dot_cw, sweeps 2 and 3 panel_sweep
+    # sweep 1 is panel_dot_cw, sweep 2 panel_sweep, sweep 3 panel_sweep or (long real panels, "stream_two") panel_update
+    is_sweep = lambda k: "panel_sweep" in k or "panel_dot_cw" in k or "panel_update" in k
     sweeps = [k for k in fetch if is_sweep(k)]
     launches = sum(fetch[k][0] for k in sweeps)
     # calibration of the gfx950 FETCH_SIZE halving on a kernel with a known read: k_scal reads n doubles
@@ -100,7 +101,7 @@ def traffic_record(sub_fetch, sub_write, shard_of):
         "command_fetch": "rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py" + flags,
         "command_write": "rocprofv3 --pmc WRITE_SIZE --output-format csv -- python3 bench.py" + flags,
         "method": "separate --pmc passes; KB units; FETCH_SIZE doubled (gfx950 reports 1/2 of a 16 B/lane streaming read, MI355X_MICROARCH.md); "
-                  "WRITE_SIZE exact; per launch = sum over the three DGS sweep kernels (panel_dot_cw, panel_sweep x2) / their launch count",
+                  "WRITE_SIZE exact; per launch = sum over the DGS sweep kernels (panel_dot_cw; panel_sweep; sweep 3 is panel_sweep or, on long real panels, panel_update) / their launch count",
         "fetch_calibration_on_k_scal(expected 2.0)": calib,
         "sweep_launches": launches,
         "fetch_bytes_per_launch_corrected": fetch_b, "write_bytes_per_launch": write_b,
