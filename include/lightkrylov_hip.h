@@ -129,10 +129,15 @@ int lk_set_partition(lk_context_t ctx, int64_t row0, int64_t n_global);
  *                 synchronisation per call; 0: one round trip per step; lk_lanczos / lk_bidiag always enqueue and do not read the key)
  *                 [bits]; "lazy", "lazy_speculate" (see lk_lazy_stats) [bits];
  *                 "pool_slab_cols" (columns per pool slab) [bits]
- *                 "fuse_rowop" (1 [default]: the asynchronous lk_arnoldi batch on a diagonal operator -- lk_linop_diag_create,
- *                 lk_linop_diag_linspace -- launches no operator kernel: the three sweeps form y = D x_k from column k-1 of the panel as
- *                 they stream it, y never exists in memory, 3k + 3 columns per step instead of 3k + 8; 0: the operator kernel writes y
- *                 first.  Same product, same summation order) [bits]
+ *                 "fuse_rowop" (the asynchronous lk_arnoldi batch on a diagonal operator -- lk_linop_diag_create, lk_linop_diag_linspace.
+ *                 0: the operator kernel writes y first.  1: no operator kernel: the three sweeps form y = D x_k from column k-1 of the
+ *                 panel as they stream it, y never exists in memory, 3k + 3 columns per step instead of 3k + 8; same product, same
+ *                 summation order as 0 [bits].  2 [default]: as 1, and on a context without a communicator, real kind, panels of at
+ *                 least 8 runs per CU ("stream_two"'s size rule: 1.68e7 rows on 256 CUs), sweep 3 of a step also forms h1 and ||y||^2
+ *                 of the NEXT step from y'' in its registers, so that step runs no sweep 1: two passes over the basis per step, 2k + 2
+ *                 columns.  h1 of steps 2.. is then (sum x (d y'')) / beta where 1 forms sum x (d (y'' / beta)): H and the basis move in
+ *                 the last bits, and a factorisation made in several calls (each call's first step runs a sweep 1) differs in the last
+ *                 bits from one call.  3: as 2 at every size)
  *   single launch "resident", "resident_max_mb", "resident_onchip", "resident_rev", "resident_spin_ms" (see lk_resident_stats)
  *   sweeps        "recompute_update" (1: sweep 2 keeps y' in registers, sweep 3 re-forms it: y' never goes to HBM; 0: y' stored, sweep 3
  *                 on the streaming update kernel -- another summation order over the columns, so y'' changes by rounding); "store_policy"

@@ -81,7 +81,6 @@ struct lk_context_s {
     bool own_stream = false;
     int num_cu = 256;
     int grid_mult = 2;  // sweep blocks per CU
-    int stream_update = 1;     // single-coefficient update sweeps: barrier-free streaming kernel
     int update_grid_mult = 4;
     int gemm_grid_mult = 4;    // panel_gemm blocks per CU
     int gemm_mfma = 1;         // tall-skinny product on the FP64 matrix cores (0: FP64 VALU kernel)
@@ -133,8 +132,10 @@ struct lk_context_s {
     // lazy batching of the PER-OBJECT path (opt-in, tuning key "lazy"): what an unchanged LightKrylov drives
     // through the type-bound procedures -- k consecutive X(i)%dot(y), then k consecutive y%axpby(a_i, X(i), 1).
     int lap5_grid_mult = 8;    // persistent blocks per CU of the stencil operator
-    int fuse_rowop = 1;        // asynchronous Arnoldi on a diagonal operator: the three sweeps form y = D x_k from column k-1 on the fly (no operator
-                               // kernel, y never in memory: 3k+3 columns per step instead of 3k+8); 0: the operator kernel writes y as before
+    int fuse_rowop = 2;        // asynchronous Arnoldi on a diagonal operator.  0: the operator kernel writes y.  1: the three sweeps form y = D x_k from
+                               // column k-1 on the fly (no operator kernel, y never in memory: 3k+3 columns per step instead of 3k+8).  2: as 1, and on one
+                               // rank without a communicator, real kind, panels of at least the "stream_two" size rule's rows, sweep 3 also forms the next
+                               // step's h1 and ||y||^2 (look-ahead: that step runs no sweep 1, 2k+2 columns).  3: as 2 at every size
     int dot_colwise = 1;       // sweep 1 by panel_dot_cw (one column at a time, y in registers) instead of panel_sweep<DOT>
     int grid_mult_s3 = 0;      // blocks per CU of the two-coefficient update sweep (0: grid_mult)
     int grid_mult_s2 = 1;      // blocks per CU of the update + dot sweep (0: grid_mult).  1 is never slower than 2 and +1-6 % at small n or small k
@@ -414,6 +415,8 @@ SweepCfg sweep_cfg(lk_context_t c, int k, int64_t n, int mult = 0) {
 //   MODE 2: y' = y - X hin ; h = X^H y'     (UPDATE+DOT), y' written only if `store`
 //   MODE 3: y' = y - X hin                  (UPDATE)
 //   MODE 4: y'' = (y - X hin) - X hin2      (UPDATE, two coefficient sets; pairs with MODE 2, store = 0)
+//   MODE 5: MODE 4 with a row operator, and the NEXT step's dots w = D y'', X^H w, y''.w, |w|^2 (look-ahead: panel_sweep's header);
+//           real kind on the narrow tile shapes only.  `out` receives k + 3 slots: the dots, ||y''||^2 in slot k, the two sums.
 // out == nullptr (update-only modes): the norm of the result is not wanted -- no finish kernel, and above all NO
 // all-reduce (the lazy flush runs at rank-dependent times; a collective there could mismatch across ranks).
 // rop.kind != ROWOP_NONE (MODE 1, 2, 4 of the asynchronous Arnoldi step on a diagonal operator): y is not read but FORMED from column
@@ -425,11 +428,11 @@ template <bool CPLX, int MODE, int KC = (CPLX ? 8 : 16), int NW = (CPLX ? 16 : 8
 int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y, int64_t n, const double *hin,
                  const double *hin2, int store, double *out, const RowOp &rop) {
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
-    constexpr bool UPDATE = MODE != 1, DOT = MODE <= 2;
+    constexpr bool UPDATE = MODE != 1, DOT = MODE <= 2;       // (the kernel's flags: the look-ahead sweep lives in the UPDATE-only instances)
     static_assert(KC * NW * SC >= KMAX_FUSED && KC * NW * SC <= KMAX_WIDE, "fused capacity");
     static_assert(G == 1 || (MODE == 4 && SC == 1), "column groups per wave: the two-coefficient sweep only");
     if (k > KC * NW * SC) return fail(LK_ERR_INVALID, "internal: sweep of %d columns on a block that holds %d", k, KC * NW * SC);
-    SweepCfg s = sweep_cfg<CPLX, KC / G, NW, SC * G>(c, k, n, MODE == 2 ? c->grid_mult_s2 : (MODE == 4 ? c->grid_mult_s3 : 0));
+    SweepCfg s = sweep_cfg<CPLX, KC / G, NW, SC * G>(c, k, n, MODE == 2 ? c->grid_mult_s2 : (MODE >= 4 ? c->grid_mult_s3 : 0));
     if (G > 1) {                             // WC and kcw are the lane-split configuration's; the tiles are G times as tall
         const int64_t tile_rows = (int64_t)(NW / s.WC) * 64 * K<CPLX>::ROWS;
         s.ntiles = (n + tile_rows - 1) / tile_rows;
@@ -441,10 +444,12 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
     }
     // ALGORITHMIC bytes of the three-sweep schedule: k+1 | k+2 | k+2 columns.  With a fused row operator y is neither
     // read nor (sweeps 1, 2) written: k | k | k+1 columns, plus the column of d an explicit diagonal reads
-    const double bytes = rop.kind != ROWOP_NONE ? (double)n * ED * 8.0 * (k + (MODE == 4 ? 1 : 0) + (rop.kind == ROWOP_DIAG ? 1 : 0))
+    const double bytes = rop.kind != ROWOP_NONE ? (double)n * ED * 8.0 * (k + (MODE >= 4 ? 1 : 0) + (rop.kind == ROWOP_DIAG ? 1 : 0))
                                                 : (double)n * ED * 8.0 * (k + 1 + (UPDATE ? 1 : 0));
     if (rop.kind != ROWOP_NONE && (MODE == 3 || !rowop_fusable<CPLX, KC>))
         return fail(LK_ERR_INVALID, "internal: this sweep takes no row operator");
+    if (MODE == 5 && (CPLX || KC != 16 || SC != 1 || k >= KMAX_FUSED || rop.kind == ROWOP_NONE || !out))
+        return fail(LK_ERR_INVALID, "internal: look-ahead sweep on a shape or an operator it does not take");
     // "stream_two": the two-coefficient sweep one column at a time (panel_update<.., true>) in sweep 2's summation order.  Bases of at most
     // KMAX_FUSED columns only: the wide register tiles (SC = 1, G = 1 too), the lane-split and the G > 1 shapes keep the tile kernel.  2 = by size: the real kind on panels long enough to give every CU several runs
     const bool col_two = MODE == 4 && SC == 1 && G == 1 && k <= KMAX_FUSED &&
@@ -503,7 +508,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             else
                 hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin, hin2,
                                    c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
-        } else if (MODE == 3 && c->stream_update) {
+        } else if (MODE == 3) {     // always the streaming kernel: the tile kernel's instances with these flags hold the look-ahead sweep
             ps.ext = false;
             if (ps.on) (void)hipEventRecord(ps.rec.e0, c->stream);
             const int64_t tile_rows = (int64_t)NW * 64 * K<CPLX>::ROWS;
@@ -516,6 +521,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y,
                                n, hin, hin2, c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), 1, k, RowOp{});
         } else {
+            // (MODE 5: panel_sweep<.., true, false, false, 1, 1>, the look-ahead body)
             const int st = (store ? (1 | (c->store_policy << 1) | (c->store_split ? 8 : 0)) : 0) | (c->xcd_map ? 16 : 0);
             if (ps.on && ps.ext)
                 hipExtLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream,
@@ -529,8 +535,8 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
     HIPCHK(hipGetLastError());
     if (!out) return LK_OK;
     // slots: DOT -> 0..k*ED-1 valid; norm at slot k*ED.  Without DOT only the norm slot is defined.
-    const int first = DOT ? 0 : k * ED;
-    const int nslots = (k + 1) * ED - first;
+    const int first = DOT || MODE == 5 ? 0 : k * ED;
+    const int nslots = (k + 1) * ED - first + (MODE == 5 ? 2 : 0);
     hipLaunchKernelGGL(finish_partials, dim3((nslots + 3) / 4), dim3(256), 0, c->stream,
                        c->partial + (int64_t)first * MAX_GRID, (int64_t)MAX_GRID, nblocks, nslots, out + first);
     HIPCHK(hipGetLastError());
@@ -538,7 +544,8 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
 }
 
 template <int MODE>
-int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const double *hin2, int store, double *out, const RowOp &rop = RowOp{}) {
+int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const double *hin2, int store, double *out, const RowOp &rop = RowOp{},
+           bool tiles16 = false) {      // tiles16: the real kind's narrow sweeps on 16-column tiles whatever "kc32" says (the sweeps of a look-ahead step)
     lk_context_t c = Bx->ctx;
     const double *X = Bx->col(c0);
     if (k > KMAX_FUSED) {
@@ -602,8 +609,8 @@ int sweepm(lk_basis_t Bx, int c0, int k, double *y, const double *hin, const dou
         // points of a scaling run compare the same kernels (round-4 advisor).  Only the DGS pair (MODE 2 + 4) takes it: the single-set
         // update (MODE 3: lazy path, one-pass orthogonalisation) keeps the 16-column tile its A/B was recorded on.
         const int64_t nref = c->n_global > 0 ? c->n_global : Bx->n;
-        const int kc32 = c->kc32 >= 0 ? c->kc32 : (nref >= ((int64_t)1 << 25) ? 32 : 0);
-        if constexpr (MODE == 2 || MODE == 4)
+        const int kc32 = tiles16 ? 0 : (c->kc32 >= 0 ? c->kc32 : (nref >= ((int64_t)1 << 25) ? 32 : 0));
+        if constexpr (MODE == 2 || MODE >= 4)
             if (kc32 && k > kc32) return launch_sweep<false, MODE, 32, 8, 1>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
     }
     return launch_sweep<false, MODE>(c, X, Bx->ld, k, y, Bx->n, hin, hin2, store, out, rop);
@@ -1179,17 +1186,18 @@ int fetch(lk_context_t c, int section0, int nsections, int stride = RED_SECTION)
     return LK_OK;
 }
 
+// la_sums / la_h1 (behind a look-ahead sweep 3): k_scal also turns that sweep's sums into the next step's h1 section
 int scal_launch(lk_basis_t B, int j, double ar, double ai, const double *inv_sqrt_of, double tol, int *stop_out = nullptr,
-                double tol_break = 0.0) {
+                double tol_break = 0.0, const double *la_sums = nullptr, double *la_h1 = nullptr) {
     lk_context_t c = B->ctx;
     const int64_t nv = B->n * B->ed() / 2 + 1;
     ProfScope ps(c, "blas1", (double)B->n * B->ed() * 16.0);
     if (B->dtype == LK_C128)
         hipLaunchKernelGGL(k_scal<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, B->col(j), B->n, ar, ai,
-                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B));
+                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B), la_sums, la_h1);
     else
         hipLaunchKernelGGL(k_scal<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, B->col(j), B->n, ar, ai,
-                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B));
+                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B), la_sums, la_h1);
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -1336,15 +1344,25 @@ int fused_sub_with_dots(lk_context_t c) {
 // Core of double_gram_schmidt_step for one vector; results stay in c->red (device):
 //   section 0: h1[0..k), nrm2(y)    section 1: h2[0..k), nrm2(y')   section 2 (slot k): nrm2(y'')
 // rop (two passes with recompute_update only): y = D X(:, c0 + k - 1) is formed inside the sweeps, `y` receives y''.
-int dgs_device(lk_basis_t Bx, int k, double *y, bool two_pass, double *red_base = nullptr, int stride = 0, int c0 = 0, const RowOp &rop = RowOp{}) {
+// Look-ahead (rop only): `have_h1` -- section 0 is already there, left by the previous step, and sweep 1 does not run; `look` -- sweep 3
+// also forms the next step's sums, k + 3 slots in section 2 (scal_launch finishes them into the next step's section 0).
+int dgs_device(lk_basis_t Bx, int k, double *y, bool two_pass, double *red_base = nullptr, int stride = 0, int c0 = 0, const RowOp &rop = RowOp{},
+               bool have_h1 = false, bool look = false) {
     lk_context_t c = Bx->ctx;
     double *base = red_base ? red_base : c->red;
     if (!stride) stride = red_stride(k);
     double *r0 = base, *r1 = base + stride, *r2 = base + 2 * stride;
     if (k <= KMAX_WIDE) {
         if (rop.kind != ROWOP_NONE && !(two_pass && c->recompute_update)) return fail(LK_ERR_INVALID, "internal: fused row operator needs the recomputing schedule");
-        LKCHK((sweepm<1>(Bx, c0, k, y, nullptr, nullptr, 1, r0, rop)));    // h1 = X^H y ; ||y||^2
+        if ((have_h1 || look) && rop.kind == ROWOP_NONE) return fail(LK_ERR_INVALID, "internal: look-ahead needs a fused row operator");
+        if (!have_h1) LKCHK((sweepm<1>(Bx, c0, k, y, nullptr, nullptr, 1, r0, rop)));    // h1 = X^H y ; ||y||^2
         if (two_pass && c->recompute_update) {
+            if (look) {
+                // the look-ahead sweep exists on 16-column tiles only, and its sweep 2 must sum in the same order: no "kc32" for this step
+                LKCHK((sweepm<2>(Bx, c0, k, y, r0, nullptr, 0, r1, rop, true)));
+                LKCHK((sweepm<5>(Bx, c0, k, y, r0, r1, 1, r2, rop, true)));     // y'' stored; ||y''||^2 and the next step's sums
+                return LK_OK;
+            }
             LKCHK((sweepm<2>(Bx, c0, k, y, r0, nullptr, 0, r1, rop)));     // y' = y - X h1 (registers only); h2 = X^H y'; ||y'||^2
             LKCHK((sweepm<4>(Bx, c0, k, y, r0, r1, 1, r2, rop)));          // y'' = (y - X h1) - X h2 ; ||y''||^2
         } else if (two_pass) {
@@ -1692,7 +1710,7 @@ int lk_set_tuning(lk_context_t c, const char *key, int value) {
         return LK_OK;
     }
     if (!strcmp(key, "dot_colwise")) { c->dot_colwise = value != 0; return LK_OK; }
-    if (!strcmp(key, "fuse_rowop")) { c->fuse_rowop = value != 0; return LK_OK; }
+    if (!strcmp(key, "fuse_rowop")) { c->fuse_rowop = value < 0 || value > 3 ? 1 : value; return LK_OK; }
     if (!strcmp(key, "cw_u")) { c->cw_u = value == 8 ? 8 : (value == 4 ? 4 : 0); return LK_OK; }
     if (!strcmp(key, "cw_grid_mult")) { if (value < 1 || value > 16) return fail(LK_ERR_INVALID, "lk_set_tuning: cw_grid_mult must be in [1, 16]"); c->cw_grid_mult = value; return LK_OK; }
     if (!strcmp(key, "xhy_db")) { c->xhy_db = value < 0 ? 0 : (value > 2 ? 2 : value); return LK_OK; }
@@ -2869,6 +2887,18 @@ static RowOp fused_rowop(lk_linop_t A, lk_basis_t X, int k, int trans) {
     return A->rowop(trans, X->dtype);
 }
 
+// Does sweep 3 of step k also form the sums of step k + 1 (panel_sweep's look-ahead), so that step k + 1 runs no sweep 1?  Both steps on
+// the three sweeps with the fused operator and the narrow tile shapes, real kind, no all-reduce between a sweep and its finish (one rank,
+// no communicator), and the routing key: 3 = always, 2 = panels long enough for the "stream_two" size rule (below it the routes of the
+// suite are compared byte for byte).
+static bool lookahead_applies(lk_linop_t A, lk_basis_t X, int k, int k1, int trans, const RowOp &rop) {
+    lk_context_t c = X->ctx;
+    if (rop.kind == ROWOP_NONE || X->dtype != LK_F64 || c->fuse_rowop < 2 || c->nranks != 1 || c->allreduce) return false;
+    if (k + 1 > k1 || k + 1 > KMAX_FUSED || resident_applies(X, k + 1)) return false;
+    if (c->fuse_rowop == 2 && X->n < (int64_t)8 * 64 * K<false>::ROWS * update_two_u<8> * c->num_cu * 8) return false;
+    return fused_rowop(A, X, k + 1, trans).kind != ROWOP_NONE;
+}
+
 constexpr int SEG_LOOKAHEAD = 24;
 constexpr int LK_STOP_REQUESTED = 1;
 static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, double tol, int trans, int *done, const int *seg_last, int nseg,
@@ -2890,6 +2920,7 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
     const size_t slot_doubles = (size_t)RED_SECTIONS * rs;
     int enq = k0;                                    // next step to enqueue
     int si = 0, seg_first = k0;                      // next segment to close, first step of it
+    bool have_h1 = false;                            // the step before `enq` looked ahead: h1 of `enq` is in its slot, no sweep 1
     auto enqueue_until = [&](int kto) -> int {       // (armed on entry, down on return: the deliveries between two calls run the caller's code)
         batch.arm();
         int rc = LK_OK;
@@ -2904,21 +2935,27 @@ static int arnoldi_batch_async(lk_linop_t A, lk_basis_t X, int k0, int k1, doubl
             if (rop.kind == ROWOP_NONE) rc = lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, k - 1, X, k);
             else X->touch(k);
             if (rc != LK_OK) break;
+            if (have_h1 && (single || rop.kind == ROWOP_NONE)) { rc = fail(LK_ERR_INVALID, "internal: look-ahead into a step that cannot use it"); break; }
+            // (decided from the batch's range, not from what will be enqueued: the last step enqueued of a batch its caller cancels has looked ahead
+            // for a step that never runs -- its section stays unread, the next call starts with a sweep 1 of its own)
+            const bool look = !single && lookahead_applies(A, X, k, k1, trans, rop);
             c->span_first = nullptr;
             // cache-resident panel: both passes, the normalise and the breakdown test in ONE launch (lk_resident.hip.h)
             if (single) rc = dgs_resident_launch(X, k, X->col(k), slot, rs, true, ATOL_DP, tol_break, c->stop_dev);
             else {
                 resident_note_fallback(X, k);
-                rc = dgs_device(X, k, X->col(k), true, slot, rs, 0, rop);
+                rc = dgs_device(X, k, X->col(k), true, slot, rs, 0, rop, have_h1, look);
             }
             if (rc != LK_OK) break;
             if (c->prof && c->span_first) {          // "dgs" = first sweep's start .. the end of the last reduction, no events of its own
                 ProfRec span;
                 span.e0 = c->span_first; span.e1 = c->span_last; span.tag = "dgs"; span.borrowed = true;
-                span.bytes = (double)X->n * ED * 8.0 * (rop.kind == ROWOP_NONE ? 3.0 * k + 5.0 : 3.0 * k + 1.0 + (rop.kind == ROWOP_DIAG ? 3.0 : 0.0));
+                span.bytes = (double)X->n * ED * 8.0 * (rop.kind == ROWOP_NONE ? 3.0 * k + 5.0 : (have_h1 ? 2.0 : 3.0) * (k + (rop.kind == ROWOP_DIAG ? 1.0 : 0.0)) + 1.0);
                 c->prof_pending.push_back(span);
             }
-            if (!single) rc = scal_launch(X, k, 1.0, 0.0, StepSlotDev{slot, rs, k, ED}.nrm2(), ATOL_DP, c->stop_dev, tol_break);
+            if (!single) rc = scal_launch(X, k, 1.0, 0.0, StepSlotDev{slot, rs, k, ED}.nrm2(), ATOL_DP, c->stop_dev, tol_break,
+                                          look ? slot + 2 * (size_t)rs : nullptr, look ? slot_of(c->step_red.get(), k + 1 - k0, rs) : nullptr);
+            have_h1 = look;
             if (rc == LK_OK && si < nseg && k == seg_last[si]) {
                 // close a segment: its slots and the stop flag as it stands now travel to the host behind this step
                 const size_t off = (size_t)(seg_first - k0) * slot_doubles;

@@ -169,8 +169,9 @@ enum { ROWOP_NONE = 0, ROWOP_LIN = 1, ROWOP_DIAG = 2 };
 // The product exactly as the operator kernel rounds it, and ROUNDED before the caller's `yv -= u` or dot FMAs see it: contraction
 // is off inside (the complex products are written out with the fused multiply-adds k_diag compiles to), and the result passes
 // through an empty asm so that no later pass can fold the multiplication into its consumer.
+// `dout` (real kind): receives d of the lane's two rows, for a sweep that applies the operator a second time (rowop_apply).
 template <bool CPLX>
-__device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict__ x, int64_t r, int64_t n, bool full) {
+__device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict__ x, int64_t r, int64_t n, bool full, v2d *dout = nullptr) {
 #pragma clang fp contract(off)
     auto ld = [&](const double *__restrict__ p) -> v2d { return load_y<CPLX>(p, r, n, full); };
     const v2d b = ld(x);
@@ -180,25 +181,37 @@ __device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict
         yv = op.conj ? diag_cmulconj(a, b) : diag_cmul(a, b);
     } else if (op.kind == ROWOP_LIN) {
         const double g = (double)(op.row0 + r);
-        yv = v2d{fma(op.dstep, g, op.d0), fma(op.dstep, g + 1.0, op.d0)} * b;
+        const v2d dv = v2d{fma(op.dstep, g, op.d0), fma(op.dstep, g + 1.0, op.d0)};
+        yv = dv * b;
+        if (dout) *dout = dv;
         if (!full) {                                   // rows beyond n are zeros whatever d_i would be there
             if (r >= n) yv.x = 0.0;
             if (r + 1 >= n) yv.y = 0.0;
         }
     } else {
-        yv = ld(op.d) * b;
+        const v2d dv = ld(op.d);
+        yv = dv * b;
+        if (dout) *dout = dv;
     }
     asm("" : "+v"(yv.x));
     asm("" : "+v"(yv.y));
     return yv;
 }
+// w = D v for rows whose d the sweep already holds (real kind): one rounded product per row, as rowop_y forms y
+__device__ __forceinline__ v2d rowop_apply(v2d dv, v2d v) {
+#pragma clang fp contract(off)
+    v2d w = dv * v;
+    asm("" : "+v"(w.x));
+    asm("" : "+v"(w.y));
+    return w;
+}
 // y of a sweep: loaded, or formed from column k-1 (`xk`) of the panel.  FUSABLE = false compiles the operator out of an instance
 // whose register tile has no room for the second stream (the launcher never hands such an instance an operator).
 template <bool CPLX, bool FUSABLE = true>
 __device__ __forceinline__ v2d load_y_op(const RowOp &op, const double *__restrict__ y, const double *__restrict__ xk, int64_t r,
-                                         int64_t n, bool full) {
+                                         int64_t n, bool full, v2d *dout = nullptr) {
     if constexpr (FUSABLE)
-        if (op.kind != ROWOP_NONE) return rowop_y<CPLX>(op, xk, r, n, full);
+        if (op.kind != ROWOP_NONE) return rowop_y<CPLX>(op, xk, r, n, full, dout);
     return load_y<CPLX>(y, r, n, full);
 }
 // complex register tiles of more than 16 columns (bases of 129..384 complex columns) are full: the explicit diagonal's second stream
@@ -260,8 +273,8 @@ __device__ __forceinline__ void load_cols_sbase(const double *__restrict__ Xt, i
 template <bool CPLX, int KC, bool UNIFORM = true, bool FUSABLE = true>
 __device__ __forceinline__ void load_tile(const double *__restrict__ Xw, int64_t colstride, const double *__restrict__ y,
                                           int64_t r, int64_t n, bool full, int nc, v2d (&xv)[KC], v2d &yv, const RowOp &rop,
-                                          const double *__restrict__ xk) {
-    yv = load_y_op<CPLX, FUSABLE>(rop, y, xk, r, n, full);
+                                          const double *__restrict__ xk, v2d *dout = nullptr) {
+    yv = load_y_op<CPLX, FUSABLE>(rop, y, xk, r, n, full, dout);
     load_cols<CPLX, KC, UNIFORM>(Xw, colstride, r, n, full, nc, xv);
 }
 
@@ -308,6 +321,19 @@ __device__ __forceinline__ void store_rows(double *__restrict__ y, int64_t r, in
 // flight: the update-only sweep has no accumulators to keep, so the registers the lane split spends on them hold columns instead.
 // (second launch bound: the narrow complex two-coefficient sweep sits at 62 of the 64 registers that let two of its 1024-thread blocks
 // share a CU -- 8 waves per SIMD; the operator's second stream must not push it over)
+//
+// LOOK-AHEAD (the asynchronous Arnoldi batch on a diagonal operator, "fuse_rowop" >= 2).  The real instance with UPDATE && !DOT && !TWO,
+// KC = 16, SC = 1, G = 1 is NOT the single-coefficient update its flags spell: that sweep always runs on panel_update (launch_sweep
+// MODE 3), so the instance was compiled and never dispatched, and it now holds sweep 3 of a step whose successor skips its sweep 1 -- the
+// same move that put the column walk into panel_update<.., true>, taken because the set of kernel instances is pinned.  (The KC = 32
+// instance of these flags stays the dormant single-coefficient update: a 32-column tile, its 32 accumulators and two coefficient sets
+// needed 176 bytes of scratch per lane, so a step that looks ahead runs its sweeps 2 and 3 on 16-column tiles.)
+// Per tile: y' = y - X h1 and y'' = y' - X h2 exactly as TWO forms them (same WC / kcw, slot order and LDS exchange order, so y'' and
+// sum |y''|^2 are TWO's bits), y'' stored; then w = D y'' with the row operator that formed y (one rounded product per row, d kept from
+// y's load), and the dots of the NEXT step against the tile still in registers: slots 0..k-1 = sum x_j w, slot k = sum |y''|^2 (where
+// it always was), slot k+1 = sum y'' w, slot k+2 = sum |w|^2.  With beta = ||y''|| the next step's vector is y_next = w / beta and its
+// last basis column y'' / beta, so k_scal turns these sums into h1 and ||y_next||^2 of step k+1 by k + 2 divisions.  Both coefficient
+// sets live in LDS and are read per use, so that the tile and its accumulators keep the registers.
 template <bool CPLX, int KC, int NW, bool UPDATE, bool DOT, bool TWO, int SC = 1, int G = 1>
 __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 : 1) void panel_sweep(const double *__restrict__ X, int64_t ldx, int k,
                                                         double *__restrict__ y, int64_t n,
@@ -324,7 +350,10 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     constexpr int ED = K<CPLX>::ELEM_DOUBLES;
     constexpr int LG = 64 / SC;          // lanes per group
     constexpr int WROWS = LG * ROWS;     // rows one wave covers per tile
-    constexpr int NU = TWO ? 2 : 1;
+    constexpr bool LA = !CPLX && KC == 16 && UPDATE && !DOT && !TWO && SC == 1 && G == 1;   // the look-ahead sweep (header comment)
+    constexpr bool T2 = TWO || LA;       // two coefficient sets
+    constexpr bool DT = DOT || LA;       // dots over the tile
+    constexpr int NU = T2 ? 2 : 1;
     constexpr bool BIG = KC > 16;        // wide register tile: scalar-base addressing (SC = 1), slim accumulators
     constexpr bool FUSE = rowop_fusable<CPLX, KC>;
 
@@ -342,20 +371,21 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     nc = nc < 0 ? 0 : nc;
 
     __shared__ v2d u_lds[UPDATE ? 2 * NU * NW * 64 : 1];
-    __shared__ double red_lds[NW * SC * (KC * ED + 1)];
+    constexpr int SLOTS = KC * ED + (LA ? 3 : 1);      // a wave's dots, the norm, and the look-ahead's two sums
+    __shared__ double red_lds[NW * SC * SLOTS];
 
     // projection coefficients of this wave's columns: wave-uniform (scalar registers) for SC = 1.  With the lane split they
     // differ from lane group to lane group and would take 2-4 VGPRs per column and coefficient set on top of the tile
     // itself (the complex two-coefficient sweep spilled): they live in LDS instead, zero padded to the block's capacity, and
     // are read back per use -- every lane of a group reads the same address (broadcast).
-    constexpr bool HLDS = SC > 1 && UPDATE;
+    constexpr bool HLDS = (SC > 1 && UPDATE) || LA;
     constexpr int CAP = KC * NW * SC;
     __shared__ double hc_lds[HLDS ? NU * CAP * ED : 1];
-    v2d hc[HLDS ? 1 : KC], hc2[(TWO && !HLDS) ? KC : 1];
+    v2d hc[HLDS ? 1 : KC], hc2[(T2 && !HLDS) ? KC : 1];
     if constexpr (HLDS) {
         for (int i = threadIdx.x; i < CAP * ED; i += NW * 64) {
             hc_lds[i] = i < k * ED ? hin[i] : 0.0;
-            if constexpr (TWO) hc_lds[CAP * ED + i] = i < k * ED ? hin2[i] : 0.0;
+            if constexpr (T2) hc_lds[CAP * ED + i] = i < k * ED ? hin2[i] : 0.0;
         }
         __syncthreads();
     } else if constexpr (UPDATE) {
@@ -378,8 +408,11 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     }
     // coefficient jj of set `set` of this lane's column group (columns beyond k read the zero padding; c0 + jj < CAP always
     // holds for the groups that own columns, and the others are clamped onto the padding's last entry)
+    int hb = c0;      // look-ahead: the wave's first coefficient, laundered once per tile so that the reads stay inside the tile loop
     auto hcoef = [&](int set, int jj) -> v2d {
-        if constexpr (HLDS) {
+        if constexpr (LA) {
+            return v2d{hc_lds[set * CAP + hb + jj], 0.0};      // (c0 + jj < WC * KC <= CAP: the zero padding covers the empty slots)
+        } else if constexpr (HLDS) {
             int idx = G > 1 ? c0 + (jj / KCG) * kcw + (jj % KCG) : c0 + jj;      // slot jj of group jj / KCG
             idx = idx < CAP ? idx : CAP - 1;
             // wide register tiles: keep the read INSIDE the tile loop (the index is laundered through an empty asm, so the
@@ -403,7 +436,7 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     for (int jj = 0; jj < (ACC1 ? 1 : KC); ++jj) acc[jj] = v2d{0.0, 0.0};
 #pragma unroll
     for (int jj = 0; jj < (ACC1 ? KC : 1); ++jj) acc1[jj] = 0.0;
-    double nrm = 0.0;
+    double nrm = 0.0, ydy = 0.0, dd = 0.0;       // sum |y_out|^2; look-ahead: sum y'' (D y''), sum |D y''|^2
 
     const int64_t tile_rows = (int64_t)WR * WROWS;
     const int64_t ntiles = (n + tile_rows - 1) / tile_rows;
@@ -426,6 +459,9 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
         const bool full = (t + 1) * tile_rows <= n;   // block-uniform
         v2d xv[KC];
         v2d yv;
+        v2d dv = v2d{0.0, 0.0};                        // look-ahead: d of the lane's rows, kept from forming y
+        v2d *const dout = LA ? &dv : nullptr;
+        if constexpr (LA) asm volatile("" : "+s"(hb));
         if constexpr (G > 1) {
             // slot g * KCG + j <- column c0 + g * kcw + j (j < kcw, column < k); the other slots hold zeros
             yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, full);
@@ -448,13 +484,13 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
             }
         } else if constexpr (BIG && SC == 1) {
             if (full) {
-                yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, true);
+                yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, true, dout);
                 load_cols_sbase<KC>(Xw + (t * tile_rows + (int64_t)wr * WROWS) * ED, colstride, (uint32_t)(rl * ROWS * ED * 8), nc, xv);
             } else {
-                load_tile<CPLX, KC, false, FUSE>(Xw, colstride, y, r, n, false, nc, xv, yv, rop, xk);
+                load_tile<CPLX, KC, false, FUSE>(Xw, colstride, y, r, n, false, nc, xv, yv, rop, xk, dout);
             }
         } else {
-            load_tile<CPLX, KC, SC == 1, FUSE>(Xw, colstride, y, r, n, full, nc, xv, yv, rop, xk);
+            load_tile<CPLX, KC, SC == 1, FUSE>(Xw, colstride, y, r, n, full, nc, xv, yv, rop, xk, dout);
         }
 
         if constexpr (UPDATE) {
@@ -490,7 +526,7 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
                 if constexpr (CPLX) u += cmul(xv[jj], hcoef(0, jj));
                 else u += xv[jj] * hcoef(0, jj).x;
             }
-            if constexpr (TWO) {
+            if constexpr (T2) {
 #pragma unroll
                 for (int jj = 0; jj < KC; ++jj) {
                     if constexpr (CPLX) u2 += cmul(xv[jj], hcoef(1, jj));
@@ -509,18 +545,18 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
             if (WC > 1) {
                 v2d *ub = u_lds + buf * (NU * NW * 64);
                 ub[wave * 64 + lane] = u;
-                if constexpr (TWO) ub[NW * 64 + wave * 64 + lane] = u2;
+                if constexpr (T2) ub[NW * 64 + wave * 64 + lane] = u2;
                 __syncthreads();
                 v2d s = v2d{0.0, 0.0}, s2 = v2d{0.0, 0.0};
                 for (int w = 0; w < WC; ++w) s += ub[(wr * WC + w) * 64 + lane];
-                if constexpr (TWO)
+                if constexpr (T2)
                     for (int w = 0; w < WC; ++w) s2 += ub[NW * 64 + (wr * WC + w) * 64 + lane];
                 u = s;
                 u2 = s2;
                 buf ^= 1;
             }
             yv -= u;
-            if constexpr (TWO) yv -= u2;
+            if constexpr (T2) yv -= u2;
             // `store`: 0 = keep y' in registers; otherwise bit 0 set, bits 1-2 = cache policy of the 16-B
             // store, bit 3 = every wave of the column split stores its own 64/WC-lane slice of the rows
             // (instead of the wc == 0 wave storing all 64 lanes).
@@ -536,20 +572,27 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
                 }
             }
         }
-        if constexpr (DOT) {
+        v2d dy = yv;                                   // what the dots run against: y_out, or the look-ahead's w = D y''
+        if constexpr (LA) dy = rowop_apply(dv, yv);
+        if constexpr (DT) {
 #pragma unroll
             for (int jj = 0; jj < KC; ++jj) {
-                if constexpr (CPLX) acc[jj] += cmulconj(xv[jj], yv);
-                else if constexpr (ACC1) acc1[jj] = fma(xv[jj].y, yv.y, fma(xv[jj].x, yv.x, acc1[jj]));
-                else acc[jj] += xv[jj] * yv;
+                if constexpr (CPLX) acc[jj] += cmulconj(xv[jj], dy);
+                else if constexpr (ACC1) acc1[jj] = fma(xv[jj].y, dy.y, fma(xv[jj].x, dy.x, acc1[jj]));
+                else acc[jj] += xv[jj] * dy;
             }
         }
-        if (wc == 0 && lg == 0) nrm += yv.x * yv.x + yv.y * yv.y;
+        if (wc == 0 && lg == 0) {
+            nrm += yv.x * yv.x + yv.y * yv.y;
+            if constexpr (LA) {
+                ydy = fma(yv.y, dy.y, fma(yv.x, dy.x, ydy));
+                dd = fma(dy.y, dy.y, fma(dy.x, dy.x, dd));
+            }
+        }
     }
 
     // ---- block reduction: lanes (shuffle) -> waves sharing a column set (LDS) -> partial
-    constexpr int SLOTS = KC * ED + 1;
-    if constexpr (DOT) {
+    if constexpr (DT) {
 #pragma unroll
         for (int jj = 0; jj < KC; ++jj) {
             if constexpr (SC == 1) {
@@ -589,11 +632,15 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     {
         double s = wave_sum(nrm);
         if (lane == 0) red_lds[(wave * SC) * SLOTS + KC * ED] = s;
+        if constexpr (LA) {
+            const double s1 = wave_sum(ydy), s2 = wave_sum(dd);
+            if (lane == 0) { red_lds[wave * SLOTS + KC + 1] = s1; red_lds[wave * SLOTS + KC + 2] = s2; }
+        }
     }
     __syncthreads();
     // thread tid < k*ED handles one output double: column j = tid/ED lives in column group j / kcw
     const int tid = threadIdx.x;
-    if constexpr (DOT) {
+    if constexpr (DT) {
         for (int o = tid; o < k * ED; o += NW * 64) {
             const int j = o / ED, part = o % ED;
             const int cgj = j / kcw, jj = j - cgj * kcw;
@@ -607,6 +654,13 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
         for (int w = 0; w < WR; ++w) s += red_lds[(w * WC * SC) * SLOTS + KC * ED];
         partial[((int64_t)k * ED) * pstride + blockIdx.x] = s;
         if constexpr (CPLX) partial[((int64_t)k * ED + 1) * pstride + blockIdx.x] = 0.0;
+    }
+    if constexpr (LA) {
+        if (tid == 1 || tid == 2) {
+            double s = 0.0;
+            for (int w = 0; w < WR; ++w) s += red_lds[(w * WC) * SLOTS + KC + tid];
+            partial[(int64_t)(k + tid) * pstride + blockIdx.x] = s;
+        }
     }
 }
 
@@ -3092,15 +3146,24 @@ __global__ __launch_bounds__(256) void finish_partials(const double *__restrict_
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_scal(double *__restrict__ x, int64_t n, double ar, double ai,
                                               const double *__restrict__ inv_sqrt_of, double tol, Guard guard,
-                                              int *__restrict__ stop_out, double tol_break, int nt) {
+                                              int *__restrict__ stop_out, double tol_break, int nt,
+                                              const double *__restrict__ la_sums, double *__restrict__ la_h1) {
     // inv_sqrt_of != NULL: alpha = 1/sqrt(|*inv_sqrt_of|) read on the device (fused normalise);
     // skipped (alpha = 1) when the norm is below tol so the host can take the breakdown path.
     // stop_out != NULL (asynchronous Arnoldi): a norm below tol_break, or a NaN, stops every LATER step.
+    // la_sums != NULL (behind a look-ahead sweep 3 of step k, panel_sweep's header): the section that holds its k + 3 sums, the norm
+    // inv_sqrt_of points at among them in slot k.  With beta = the norm, block 0 leaves in la_h1 what sweep 1 of step k + 1 would have:
+    // h1[j] = sums[j] / beta (j < k), h1[k] = sums[k+1] / beta^2, and ||y_next||^2 = sums[k+2] / beta^2 behind them.
     if (stopped(guard)) return;
     if (inv_sqrt_of) {
         const double nr = sqrt(fabs(*inv_sqrt_of));
         if (stop_out && blockIdx.x == 0 && threadIdx.x == 0 && !(nr >= tol_break)) *stop_out = guard.step;
         if (!(nr >= tol)) return;
+        if (la_sums && blockIdx.x == 0) {
+            const int k = (int)(inv_sqrt_of - la_sums), j = threadIdx.x;
+            if (j < k) la_h1[j] = la_sums[j] / nr;
+            else if (j < k + 2) la_h1[j] = la_sums[j + 1] / fabs(*inv_sqrt_of);
+        }
         ar = 1.0 / nr;
         ai = 0.0;
     }

@@ -91,11 +91,21 @@ def traffic_record(sub_fetch, sub_write, shard_of):
     # the diagonal operator is applied inside the sweeps ("fuse_rowop"): k | k | k + 1 columns per step, y is never
     # read and only y'' is written -- algorithmic bytes and what the schedule must move are the same 3k + 1 columns
     alg = 8.0 * n_local * sum(3 * k + 1 for k in range(1, m + 1)) / (3.0 * m)
+    # look-ahead ("fuse_rowop" = 2 on long real panels of one rank): sweep 3 of a step forms the next step's h1, so sweep 1 runs for the first
+    # step only -- k columns for that launch, then k | k + 1 per step, on 2 m + 1 launches.  Recognised by the kernel that ran: the look-ahead
+    # sweep is the tile kernel's UPDATE-only instance, which no other schedule dispatches.  (A short panel's first steps take the single
+    # launch, so its sweep-1 count is below m on three sweeps too.)
+    lookahead = any("panel_sweep<false, 16, 8, true, false, false, 1, 1>" in k for k in fetch)
+    if lookahead:
+        alg = 8.0 * n_local * (1 + sum(2 * k + 1 for k in range(1, m + 1))) / (2.0 * m + 1.0)
     must = alg
-    flags = " --steps 1 --warmup 0 --no-cpu-baseline" + (f" --shard-of {shard_of}" if shard_of > 1 else "")
+    # a rank of a P-rank job has a communicator and so runs three sweeps; one row block alone on a GPU has none and would look ahead:
+    # the shard records are taken with "fuse_rowop" = 1, the schedule the ranks run
+    flags = " --steps 1 --warmup 0 --no-cpu-baseline" + (f" --shard-of {shard_of} --tune fuse_rowop=1" if shard_of > 1 else "")
     name = f"{tag}_pmc_n{n_local:.3g}_m{m}.json".replace("+0", "").replace("+", "")
     pm = {
         "commit": commit, "kernel_source_sha256": khash, "n_local": n_local, "m": m, "dtype": "f64",
+        "schedule": "look-ahead: sweep 1 once, then sweeps 2 and 3 per step" if lookahead else "three sweeps per step",
         "shard": (f"rank 0's row block of a {shard_of}-rank job (n_global = {pb.get('config', {}).get('n_global')}), alone on one GPU: bench.py --shard-of {shard_of}"
                   if shard_of > 1 else "the single-GPU workload"),
         "command_fetch": "rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py" + flags,
