@@ -61,6 +61,7 @@ module lightkrylov_gpu
     public :: gpu_arnoldi_segments_rdp, gpu_arnoldi_segments_cdp, lk_gpu_progress
     public :: gpu_lanczos_rdp, gpu_lanczos_cdp, gpu_bidiag_rdp, gpu_bidiag_cdp, gpu_qr_rdp, gpu_qr_cdp
     public :: gpu_kexpm_rdp, gpu_kexpm_cdp
+    public :: gpu_qr_pivot_rdp, gpu_qr_pivot_cdp, gpu_kexpm_block_rdp, gpu_kexpm_block_cdp
 
     type(c_ptr), save :: ctx = c_null_ptr
     integer(c_int64_t), save :: part_row0 = 0          ! first global row of this rank's block (lk_gpu_set_partition)
@@ -997,5 +998,80 @@ contains
         integer, optional, intent(in) :: kdim
         real(dp), optional, intent(out) :: err_est
         call gpu_kexpm_rdp(Bc, jc, op, Bb, jb, X, tau, tol, info, trans, kdim, err_est)
+    end subroutine
+
+    !> qr_with_pivoting (src/Krylov/qr.fypp:32-107) of columns j0+1 .. j0+size(R, 2) of the panel Q (j0 defaults to 0); R is p x p,
+    !> perm holds the column ordering, 1-based as in the reference.
+    subroutine gpu_qr_pivot_rdp(Q, R, perm, info, tol, j0)
+        type(c_ptr), intent(in) :: Q
+        real(dp), intent(inout) :: R(:, :)
+        integer, intent(out) :: perm(:)
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: tol
+        integer, optional, intent(in) :: j0
+        integer(c_int) :: cinfo, c0
+        integer(c_int) :: cperm(size(R, 2))
+        real(c_double) :: tl
+        c0 = 0; if (present(j0)) c0 = j0
+        tl = 10.0_dp**(-precision(1.0_dp)); if (present(tol)) tl = tol
+        call chk(lk_qr_pivot(Q, c0, int(size(R, 2), c_int), R, int(size(R, 1), c_int64_t), cperm, tl, cinfo), 'gpu_qr_pivot_rdp')
+        perm(:size(R, 2)) = cperm
+        info = cinfo
+    end subroutine
+
+    subroutine gpu_qr_pivot_cdp(Q, R, perm, info, tol, j0)
+        type(c_ptr), intent(in) :: Q
+        complex(dp), intent(inout), target, contiguous :: R(:, :)
+        integer, intent(out) :: perm(:)
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: tol
+        integer, optional, intent(in) :: j0
+        integer(c_int) :: cinfo, c0
+        integer(c_int) :: cperm(size(R, 2))
+        real(c_double) :: tl
+        real(c_double), pointer :: Rr(:)
+        c0 = 0; if (present(j0)) c0 = j0
+        tl = 10.0_dp**(-precision(1.0_dp)); if (present(tol)) tl = tol
+        call c_f_pointer(c_loc(R), Rr, [2*size(R)])
+        call chk(lk_qr_pivot(Q, c0, int(size(R, 2), c_int), Rr, int(size(R, 1), c_int64_t), cperm, tl, cinfo), 'gpu_qr_pivot_cdp')
+        perm(:size(R, 2)) = cperm
+        info = cinfo
+    end subroutine
+
+    !> kexpm, block form (kexpm_mat, src/Expm/ExpmLib.fypp:234-363) as ONE engine call (lk_kexpm_block): columns jc0 .. jc0+p-1 (0-based)
+    !> of the panel Bc become exp(tau op(A)) times columns jb0 .. jb0+p-1 of Bb.  nk = kdim * p block steps at most (:276; kdim defaults
+    !> to the reference's 100, cut to nk = 512 / p - 1 when kdim is absent); X: the caller's workspace panel of at least p (nk + 1) <= 512 columns.  info as in the reference: kpp > 0
+    !> converged with kpp Krylov vectors, -1 not converged.  The handles carry the kind: the two names exist for symmetry.
+    subroutine gpu_kexpm_block_rdp(Bc, jc0, op, Bb, jb0, p, X, tau, tol, info, trans, kdim, err_est)
+        type(c_ptr), intent(in) :: Bc, op, Bb, X
+        integer, intent(in) :: jc0, jb0, p
+        real(dp), intent(in) :: tau, tol
+        integer, intent(out) :: info
+        logical, optional, intent(in) :: trans
+        integer, optional, intent(in) :: kdim
+        real(dp), optional, intent(out) :: err_est
+        integer(c_int) :: cinfo, tr, nk
+        real(c_double) :: err
+        tr = 0; if (present(trans)) tr = merge(1, 0, trans)
+        nk = 100; if (present(kdim)) nk = kdim                                ! kmax, ExpmLib.fypp:255
+        nk = nk*p                                                             ! :276
+        ! the engine takes at most 512 workspace columns: WITHOUT kdim the reference's default (p (100 p + 1) vectors) is cut to the
+        ! 512 / p - 1 block steps that fit, as the Python mirror does; X must hold p (nk + 1) columns.  A kdim passed in is taken as is.
+        if (.not. present(kdim)) nk = max(min(nk, 512/p - 1), 1)
+        call chk(lk_kexpm_block(op, tr, Bb, int(jb0, c_int), Bc, int(jc0, c_int), int(p, c_int), X, tau, tol, nk, cinfo, err), &
+                 'gpu_kexpm_block')
+        info = cinfo
+        if (present(err_est)) err_est = err
+    end subroutine
+
+    subroutine gpu_kexpm_block_cdp(Bc, jc0, op, Bb, jb0, p, X, tau, tol, info, trans, kdim, err_est)
+        type(c_ptr), intent(in) :: Bc, op, Bb, X
+        integer, intent(in) :: jc0, jb0, p
+        real(dp), intent(in) :: tau, tol
+        integer, intent(out) :: info
+        logical, optional, intent(in) :: trans
+        integer, optional, intent(in) :: kdim
+        real(dp), optional, intent(out) :: err_est
+        call gpu_kexpm_block_rdp(Bc, jc0, op, Bb, jb0, p, X, tau, tol, info, trans, kdim, err_est)
     end subroutine
 end module lightkrylov_gpu

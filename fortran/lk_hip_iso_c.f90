@@ -510,6 +510,38 @@ module lightkrylov_hip_c
             real(c_double), intent(out) :: err_est
             integer(c_int) :: rc
         end function
+        !> largest singular value of a small m x n matrix on the host (norm(., 2) of ExpmLib.fypp:346); dtype = LK_F64 / LK_C128, lda in elements
+        function lk_norm2_dense(dtype, m, n, A, lda, res) bind(C, name="lk_norm2_dense") result(rc)
+            import :: c_int, c_double, c_int64_t
+            integer(c_int), value :: dtype, m, n
+            real(c_double), intent(in) :: A(*)
+            integer(c_int64_t), value :: lda
+            real(c_double), intent(out) :: res
+            integer(c_int) :: rc
+        end function
+        !> qr_with_pivoting (qr.fypp:32-107) of columns [j0, j0 + p) of the panel Q; R p x p (ldr in elements), perm 1-based
+        function lk_qr_pivot(Q, j0, p, R, ldr, perm, tol, info) bind(C, name="lk_qr_pivot") result(rc)
+            import :: c_int, c_ptr, c_double, c_int64_t
+            type(c_ptr), value :: Q
+            integer(c_int), value :: j0, p
+            real(c_double), intent(inout) :: R(*)
+            integer(c_int64_t), value :: ldr
+            integer(c_int), intent(inout) :: perm(*)
+            real(c_double), value :: tol
+            integer(c_int), intent(out) :: info
+            integer(c_int) :: rc
+        end function
+        !> kexpm, block form (kexpm_mat, ExpmLib.fypp:234-363): columns [jc0, jc0 + p) of Bc = exp(tau op(A)) (columns [jb0, jb0 + p) of Bb);
+        !> nk block steps at most, X = workspace of >= p (nk + 1) columns
+        function lk_kexpm_block(A, trans, Bb, jb0, Bc, jc0, p, X, tau, tol, nk, info, err_est) bind(C, name="lk_kexpm_block") result(rc)
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: A, Bb, Bc, X
+            integer(c_int), value :: trans, jb0, jc0, p, nk
+            real(c_double), value :: tau, tol
+            integer(c_int), intent(out) :: info
+            real(c_double), intent(out) :: err_est
+            integer(c_int) :: rc
+        end function
     end interface
 
 contains

@@ -492,10 +492,53 @@ int lk_expm_dense(int dtype, int n, const double *A, int64_t lda, double *E, int
  * tol -- c is then the kdim-step approximation (:223-231).  err_est may be NULL.
  * LK_ERR_INVALID, with nothing written: kdim out of range; c a column of X, or the same column as b; b one of the columns
  * [0, kdim] of X; operator and vectors of different shape, kind or context; a ROW-SHARDED context (nranks > 1).
- * Not provided: kexpm_mat (:234-363, the block variant, which needs the column-pivoting qr), row-sharded contexts, and the
- * Newton-Krylov layer built on the propagator. */
+ * Not provided: row-sharded contexts, and the Newton-Krylov layer built on the propagator. */
 int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int jc, lk_basis_t X, double tau, double tol, int kdim,
              int *info, double *err_est);
+
+/* ---- qr_with_pivoting and the block form of kexpm ------------------------------------------------------------------
+ * Largest singular value of an m x n column-major matrix of `dtype` (lda in elements): `norm(., 2)` of stdlib_linalg, which
+ * ExpmLib.fypp:346 applies to the small p x p block of kexpm_mat's error estimate.  HOST ONLY, like the dense exponential above -- no
+ * context, no device, no LAPACK: one-sided Jacobi (Hestenes) rotations on a packed copy (csrc/lk_expm.h).  m or n = 0 gives
+ * out = 0 and LK_OK; a negative size, a null pointer or lda < m is LK_ERR_INVALID. */
+int lk_norm2_dense(int dtype, int m, int n, const double *A, int64_t lda, double *out);
+/* qr_with_pivoting(Q, R, perm, info, tol): src/Krylov/qr.fypp:32-107 (swap_columns :176-202), on columns [j0, j0 + p) of a panel,
+ * p <= 512.  R: host p x p column-major (leading dimension ldr elements) of the basis dtype, zeroed by the call (:42; rows p..ldr-1
+ * are not touched); perm: p ints, 1-BASED like the reference's (:49): on return column i of Q R is column perm(i) of the input.
+ * Rii(i) = Q(i)%dot(Q(i)) (:50) comes from multi-column dot passes, four columns each.  Column j: the first maximum of |Rii| (:54; a
+ * NaN counts as the largest, so a column that holds one is taken at once and ends the call at the norm test) below
+ * tol => columns j..p are re-drawn from the counter generator (stream 0x5EED + panel column + 1, as the re-draw of the unpivoted
+ * factorisation above), each orthogonalised against the columns before it and normalised, info = j, and the loop exits (:55-66).
+ * Otherwise columns j and idx are exchanged IN PLACE on the device (one kernel, two reads and two writes per element, no temporary;
+ * :192-194 are three copies through a fresh vector) together with R(:min(j, idx) - 1, .), Rii and perm (:196-201); beta = ||q_j||
+ * (:71), NaN => LK_ERR_NAN "|beta| = NaN detected! Abort" (:73-77); |beta| < tol => info = j, R(j, j) = 0, re-draw, Gram-Schmidt, new
+ * norm (:79-85; the reference hands `info` to that Gram-Schmidt step, which clears it again: here it stays j), else R(j, j) = beta;
+ * q_j scaled (:90).  The trailing update (:93-97) is ONE classical pass, as there, but over all remaining columns at once:
+ * h = q_j^H Q(:, j+1:p) by the multi-column dot kernel and Q(:, j+1:p) -= q_j h by the tall-skinny product, four columns per launch
+ * pair, one host synchronisation per column j; R(j, i) = h_i.  Rii(i) -= R(j, i)**2 (:100-103) on the host -- for the complex kind
+ * Rii is complex and that is the complex SQUARE, not |R(j, i)|^2, as in the reference.
+ * Host-synchronous.  No device memory is allocated beyond the context's grow-once workspaces.
+ * LK_ERR_INVALID, with nothing written: a null argument, a bad column range, p > 512, ldr < p, and a ROW-SHARDED context (nranks > 1:
+ * the re-draw and the reductions of this schedule have not been walked through for a row partition). */
+int lk_qr_pivot(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, int *perm, double tol, int *info);
+/* kexpm(C, A, B, tau, tol, info, trans, kdim), block form (kexpm_mat): src/Expm/ExpmLib.fypp:234-363.  C = columns [jc0, jc0 + p) of Bc
+ * (overwritten) ~ exp(tau op(A)) B, B = columns [jb0, jb0 + p) of Bb (read only).  nk: the largest number of BLOCK Arnoldi steps (the
+ * reference sets nk = kdim * p, :276; the mirrors compute it).  X: workspace of the CALLER with at least p (nk + 1) <= 512 columns of
+ * the same context, dtype and n_local; on return it holds the block Krylov basis.  No device memory is allocated beyond the context's
+ * grow-once workspaces.
+ * Start: X(:, :p) = B, pivoting qr with tolerance atol_dp (its info is discarded, :297), R := permcols(R, invperm(perm)); ||R||_F = 0
+ * gives C = 0, kpp = p and err_est = 0 (:299-302); else the unpivoted qr of the orthonormal block that initialize_krylov_subspace
+ * runs (:304, src/Krylov/utilities.fypp:44-46).  Step k = 1..nk (:306-351): ONE block Arnoldi step (kstart = kend = k, tolerance
+ * atol_dp, :314), kp = k p; info = kp there => kpp = kp (:317-321), else kpp = kp + p; E = expm(tau H(:kpp, :kpp)) (:324);
+ * err_est = 0 after a breakdown, else the spectral norm of E(kp+1:kpp, :p) R (:342-347); stop at err_est <= tol (:349).  One host
+ * synchronisation per step (no look-ahead as in the vector form above).  The projection C = X(:, :kpp) (E(:kpp, :p) R) runs ONCE behind the loop,
+ * the small product on the host (:327-339 repeat it after every step and keep the last).
+ * info = kpp when err_est <= tol, else -1 -- C is then the nk-step approximation (:354-362).  err_est may be NULL.
+ * LK_ERR_INVALID, with nothing written: p < 1; nk < 1 or p (nk + 1) beyond the workspace or 512; a column of C inside X or shared with
+ * B; a column of B among the columns [0, p (nk + 1)) of X; operator and panels of different shape, kind or context; a ROW-SHARDED
+ * context (nranks > 1). */
+int lk_kexpm_block(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t Bc, int jc0, int p, lk_basis_t X, double tau, double tol,
+                   int nk, int *info, double *err_est);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,9 @@ SIGNATURES = {
     "lk_arnoldi_block": (_int, [_p, _p, _dp, _i64, _int, _int, _int, C.c_double, _int, _ip]),
     "lk_expm_dense": (_int, [_int, _int, _dp, _i64, _dp, _i64]),
     "lk_kexpm": (_int, [_p, _int, _p, _int, _p, _int, _p, C.c_double, C.c_double, _int, _ip, _dp]),
+    "lk_norm2_dense": (_int, [_int, _int, _int, _dp, _i64, _dp]),
+    "lk_qr_pivot": (_int, [_p, _int, _int, _dp, _i64, _ip, C.c_double, _ip]),
+    "lk_kexpm_block": (_int, [_p, _int, _p, _int, _p, _int, _int, _p, C.c_double, C.c_double, _int, _ip, _dp]),
 }
 
 

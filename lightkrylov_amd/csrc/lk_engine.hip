@@ -2363,7 +2363,22 @@ int lk_vec_copy(lk_basis_t Bd, int jd, lk_basis_t Bs, int js) {
     ProfScope ps(Bd->ctx, "blas1", (double)Bd->n * Bd->ed() * 16.0);
     const int64_t nd = Bd->n * Bd->ed();
     hipLaunchKernelGGL(k_copy, dim3(blas1_grid(Bd->ctx, nd / 2 + 1)), dim3(256), 0, Bd->ctx->stream, Bs->col(js), Bd->col(jd), nd,
-                       blas1_nt(Bd));
+                       blas1_nt(Bd), 0);
+    HIPCHK(hipGetLastError());
+    return LK_OK;
+}
+
+// swap_columns(Q, ..., i, j), the vector part (qr.fypp:192-194: copy(Qwrk, Q(j)); copy(Q(j), Q(i)); copy(Q(i), Qwrk) through a freshly
+// allocated Qwrk): columns i and j of B exchanged in place by k_copy's swap path -- 32 bytes of traffic per element instead of 48, no
+// temporary.  Engine-internal: the caller has validated the columns and entered the lazy layer.
+static int swap_columns(lk_basis_t B, int i, int j) {
+    if (i == j) return LK_OK;
+    lk_context_t c = B->ctx;
+    B->touch(i);
+    B->touch(j);
+    ProfScope ps(c, "blas1", (double)B->n * B->ed() * 32.0);
+    const int64_t nd = B->n * B->ed();
+    hipLaunchKernelGGL(k_copy, dim3(blas1_grid(c, nd / 2 + 1)), dim3(256), 0, c->stream, B->col(i), B->col(j), nd, blas1_nt(B), 1);
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -3385,6 +3400,127 @@ int lk_qr(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, double tol, int *
     return qr_columns_sync(Q, j0, p, 0, false, 0.0, R, ldr, tol, &flag, info);
 }
 
+// ---- qr_with_pivoting (qr.fypp:32-107) ----------------------------------------------------------------------------------------------
+// The one-column basis q against up to four columns of Y per pass (dots_p): group g of the columns [jy0, jy0 + m) leaves its sections at
+// `out` + g * QRP_GROUP * ED doubles, so column i of the run finds (q^H y_i, ||y_i||^2) at out[(2 i) * ED], out[(2 i + 1) * ED] whatever
+// the group widths -- panel_dot_p's [q][k + 1][ED] layout with k = 1.  `update`: Y(:, group) -= q (q^H Y(:, group)) behind each group's
+// dots, coefficients read where the dots left them (one pass of dgs_block_walk's four-pass schedule).
+constexpr int QRP_GROUP = 4 * 2;              // doubles (real kind) one group of four right-hand sides fills: 4 x (k + 1), k = 1
+static int qr_pivot_dots(lk_basis_t Q, int jq, int jy0, int m, double *out, bool update) {
+    lk_basis_s qv = basis_view(Q, jq, 1);
+    const int ED = Q->ed();
+    for (int g = 0; 4 * g < m; ++g) {
+        const int pn = (m - 4 * g) < 4 ? (m - 4 * g) : 4;
+        double *sec = out + (size_t)g * QRP_GROUP * ED;
+        LKCHK(dots_p(&qv, 0, 1, Q, jy0 + 4 * g, pn, sec));
+        if (update) LKCHK(gemm_subtract(&qv, 1, Q, jy0 + 4 * g, pn, sec, 2));
+    }
+    return LK_OK;
+}
+
+static int qr_pivot_impl(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, int *perm, double tol, int *info);
+
+int lk_qr_pivot(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, int *perm, double tol, int *info) {
+    if (!Q || !R || !perm || !info) return fail(LK_ERR_INVALID, "lk_qr_pivot: null argument");
+    if (p < 1 || j0 < 0 || j0 + p > Q->ncols) return fail(LK_ERR_INVALID, "lk_qr_pivot: bad column range");
+    if (p > KMAX_WIDE) return fail(LK_ERR_INVALID, "lk_qr_pivot: at most %d columns (got %d)", KMAX_WIDE, p);
+    if (ldr < p) return fail(LK_ERR_INVALID, "lk_qr_pivot: ldr too small");
+    lk_context_t c = Q->ctx;
+    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_qr_pivot: row-sharded contexts (nranks = %d) are not supported", c->nranks);
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    try {
+        return qr_pivot_impl(Q, j0, p, R, ldr, perm, tol, info);
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_qr_pivot: no host memory for the work arrays of %d columns", p);
+    }
+}
+
+// the factorisation itself: arguments validated, device selected and the lazy layer entered by the caller (lk_qr_pivot, lk_kexpm_block)
+static int qr_pivot_impl(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, int *perm, double tol, int *info) {
+    lk_context_t c = Q->ctx;
+    const int ED = Q->ed();
+    typedef std::complex<double> cplx;
+    auto Rat = [&](int i, int j) { return R + ((size_t)j * ldr + i) * ED; };
+    auto sections = [&](int m) { return (int)((((size_t)(m + 3) / 4) * QRP_GROUP * ED + RED_SECTION - 1) / RED_SECTION); };
+    *info = 0;
+    for (int j = 0; j < p; ++j) {
+        for (int i = 0; i < p * ED; ++i) Rat(0, j)[i] = 0.0;                                   // R = zero      :42
+        perm[j] = j + 1;                                                                       // :49
+    }
+    Q->touch(j0, p);
+    // Rii(i) = Q(i)%dot(Q(i)) (:50), all columns in passes of four: the norm slot of the multi-column dot (the dots against Q(1) beside
+    // it are not used).  Of the basis kind like the reference's: the complex one keeps a complex Rii (imaginary part zero here).
+    std::vector<cplx> Rii(p);
+    LKCHK(qr_pivot_dots(Q, j0, j0, p, c->red, false));
+    LKCHK(fetch(c, 0, sections(p)));
+    for (int i = 0; i < p; ++i) Rii[i] = cplx(c->red_host[(size_t)(2 * i + 1) * ED], 0.0);
+    // re-draw of column i (:57-60, :82-85): the counter generator on the stream qr_no_pivoting's re-draw uses, orthogonalised against the
+    // columns before it, its new norm
+    auto redraw = [&](int i, double *beta) -> int {
+        LKCHK(lk_vec_rand(Q, j0 + i, QR_SEED + (uint64_t)(j0 + i) + 1, c->row0, 0));
+        if (i > 0) {
+            lk_basis_s Qv = basis_view(Q, j0, i);
+            int dinfo = 0;
+            LKCHK(lk_dgs(&Qv, i, Q, j0 + i, nullptr, nullptr, 0, &dinfo));
+        }
+        return lk_vec_norm(Q, j0 + i, beta);
+    };
+    for (int j = 0; j < p; ++j) {
+        int idx = 0;                                                                           // maxloc(abs(Rii)): the first maximum  :54
+        double big = std::abs(Rii[0]);
+        for (int i = 1; i < p; ++i) {
+            // (a NaN counts as the largest: what maxloc makes of one is left to the compiler, and a column that holds one is then
+            //  taken at once and stops the call at the norm test below instead of travelling through R)
+            const double a = std::abs(Rii[i]);
+            if (a > big || (a != a && big == big)) { big = a; idx = i; }
+        }
+        if (big < tol) {                                                                       // breakdown  :55-66
+            for (int i = j; i < p; ++i) {
+                double beta = 0.0;
+                LKCHK(redraw(i, &beta));
+                const double inv[2] = {1.0 / beta, 0.0};
+                LKCHK(lk_vec_scal(Q, j0 + i, inv));
+            }
+            *info = j + 1;
+            break;
+        }
+        if (idx != j) {                                                                        // swap_columns  :68, :176-202
+            LKCHK(swap_columns(Q, j0 + j, j0 + idx));
+            std::swap(Rii[j], Rii[idx]);
+            std::swap(perm[j], perm[idx]);
+            const int nr = (j < idx ? j : idx) * ED;
+            for (int i = 0; i < nr; ++i) std::swap(Rat(0, j)[i], Rat(0, idx)[i]);
+        }
+        double beta = 0.0;
+        LKCHK(lk_vec_norm(Q, j0 + j, &beta));                                                  // :71
+        if (beta != beta) return fail(LK_ERR_NAN, "|beta| = NaN detected! Abort");               // :73-77
+        if (std::fabs(beta) < tol) {                                                           // :79-85
+            *info = j + 1;
+            set_real(Rat(j, j), ED, 0.0);
+            LKCHK(redraw(j, &beta));
+        } else {
+            set_real(Rat(j, j), ED, beta);                                                     // :87
+        }
+        const double inv[2] = {1.0 / beta, 0.0};
+        LKCHK(lk_vec_scal(Q, j0 + j, inv));                                                    // :90
+        // h = q_j^H Q(:, j+1:p), Q(:, j+1:p) -= q_j h, R(j, i) = h_i: ONE pass (:93-97), every trailing column in it
+        const int m = p - j - 1;
+        if (m > 0) {
+            LKCHK(qr_pivot_dots(Q, j0 + j, j0 + j + 1, m, c->red, true));
+            LKCHK(fetch(c, 0, sections(m)));
+            for (int i = 0; i < m; ++i)
+                for (int e = 0; e < ED; ++e) Rat(j, j + 1 + i)[e] = c->red_host[(size_t)(2 * i) * ED + e];
+        }
+        Rii[j] = 0.0;                                                                          // :100-103
+        for (int i = j + 1; i < p; ++i) {
+            const cplx r = ED == 2 ? cplx(Rat(j, i)[0], Rat(j, i)[1]) : cplx(Rat(j, i)[0], 0.0);
+            Rii[i] -= r * r;                                                                   // R(j, i)**2: the complex SQUARE, not |R|^2
+        }
+    }
+    return LK_OK;
+}
+
 // Block Arnoldi steps [k0, k1] enqueued back to back (arnoldi.fypp:34-73 with blksize = p): p operator applications, the panel x panel
 // Gram-Schmidt of the new block against X(:, :kp), and qr_no_pivoting of the block column by column -- column j's single-vector step
 // against the j columns before it (the single launch of lk_resident.hip.h for cache-resident panels), its norm and scale with the device
@@ -3428,6 +3564,29 @@ static int arnoldi_block_batch(lk_linop_t A, lk_basis_t X, int p, int k0, int k1
     return batch.finish(&stop_seq);                                      // (the caller reads *c->stop_host)
 }
 
+// One block Arnoldi step on the host-synchronous schedule (wide bases, "async_arnoldi" = 0, the last step of a call, and every step of
+// lk_kexpm_block): p operator applications, the block Gram-Schmidt and the p-column qr through the entries of the ABI, one round trip
+// each; *stop = the smallest |diagonal| of the new block is below tol (arnoldi.fypp:58-62).  Arguments validated by the caller.
+static int arnoldi_block_step_sync(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int p, int k, double tol, int trans, int *stop) {
+    const int ED = X->ed();
+    auto Hat = [&](int i, int j) { return H + ((size_t)j * ldh + i) * ED; };
+    const int kpm = (k - 1) * p, kp = k * p;
+    for (int i = 0; i < p; ++i) LKCHK(lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, kpm + i, X, kp + i));
+    std::vector<double> hb((size_t)kp * p * ED), R((size_t)p * p * ED, 0.0);
+    int dinfo = 0;
+    lk_basis_s Yv = basis_view(X, kp, p);
+    LKCHK(lk_dgs_block(X, kp, &Yv, 0, p, hb.data(), &dinfo));
+    for (int q = 0; q < p; ++q) memcpy(Hat(0, kpm + q), hb.data() + (size_t)q * kp * ED, (size_t)kp * ED * sizeof(double));
+    int qinfo = 0;
+    bool flag = false;
+    LKCHK(qr_columns_sync(X, kp, p, 0, false, 0.0, R.data(), p, ATOL_DP, &flag, &qinfo));
+    for (int q = 0; q < p; ++q) memcpy(Hat(kp, kpm + q), R.data() + (size_t)q * p * ED, (size_t)p * ED * sizeof(double));
+    double mn = HUGE_VAL;
+    for (int i = 0; i < p; ++i) mn = std::fmin(mn, std::fabs(Hat(kp + i, kpm + i)[0]));                            // :58-62 (real part)
+    *stop = mn < tol;
+    return LK_OK;
+}
+
 int lk_arnoldi_block(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int blksize, int kstart, int kend, double tol, int trans, int *info) {
     if (!A || !X || !H || !info) return fail(LK_ERR_INVALID, "lk_arnoldi_block: null argument");
     const int p = blksize;
@@ -3443,30 +3602,12 @@ int lk_arnoldi_block(lk_linop_t A, lk_basis_t X, double *H, int64_t ldh, int blk
     *info = 0;
     LKCHK(lazy_enter(c, true));
     auto Hat = [&](int i, int j) { return H + ((size_t)j * ldh + i) * ED; };
-    // one step on the host-synchronous schedule (wide bases, "async_arnoldi" = 0): the entries of the ABI, one round trip each
-    auto step_sync = [&](int k, int *stop) -> int {
-        const int kpm = (k - 1) * p, kp = k * p;
-        for (int i = 0; i < p; ++i) LKCHK(lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, X, kpm + i, X, kp + i));
-        std::vector<double> hb((size_t)kp * p * ED), R((size_t)p * p * ED, 0.0);
-        int dinfo = 0;
-        lk_basis_s Yv = basis_view(X, kp, p);
-        LKCHK(lk_dgs_block(X, kp, &Yv, 0, p, hb.data(), &dinfo));
-        for (int q = 0; q < p; ++q) memcpy(Hat(0, kpm + q), hb.data() + (size_t)q * kp * ED, (size_t)kp * ED * sizeof(double));
-        int qinfo = 0;
-        bool flag = false;
-        LKCHK(qr_columns_sync(X, kp, p, 0, false, 0.0, R.data(), p, ATOL_DP, &flag, &qinfo));
-        for (int q = 0; q < p; ++q) memcpy(Hat(kp, kpm + q), R.data() + (size_t)q * p * ED, (size_t)p * ED * sizeof(double));
-        double mn = HUGE_VAL;
-        for (int i = 0; i < p; ++i) mn = std::fmin(mn, std::fabs(Hat(kp + i, kpm + i)[0]));                            // :58-62 (real part)
-        *stop = mn < tol;
-        return LK_OK;
-    };
     int k = kstart;
     while (k <= kend) {
         int stop = 0;
         const bool wide = (int64_t)(kend + 1) * p > KMAX_WIDE || !dgs_block_fused_ok(X, k * p, X, k * p, p);
         if (!c->async_arnoldi || wide || k == kend) {
-            LKCHK(step_sync(k, &stop));
+            LKCHK(arnoldi_block_step_sync(A, X, H, ldh, p, k, tol, trans, &stop));
             if (stop) { *info = k * p; break; }                                                                       // :65-71
             ++k;
             continue;
@@ -3553,6 +3694,21 @@ int lk_expm_dense(int dtype, int n, const double *A, int64_t lda, double *E, int
             lk_expm::expm(n, A, lda, E, lde);
     } catch (const std::bad_alloc &) {
         return fail(LK_ERR_NOMEM, "lk_expm_dense: no host memory for the work arrays of a %d x %d matrix", n, n);
+    }
+    return LK_OK;
+}
+
+int lk_norm2_dense(int dtype, int m, int n, const double *A, int64_t lda, double *out) {
+    if (dtype != LK_F64 && dtype != LK_C128) return fail(LK_ERR_INVALID, "lk_norm2_dense: unknown dtype %d", dtype);
+    if (m < 0 || n < 0) return fail(LK_ERR_INVALID, "lk_norm2_dense: m = %d, n = %d", m, n);
+    if (!out) return fail(LK_ERR_INVALID, "lk_norm2_dense: null argument");
+    if (m == 0 || n == 0) { *out = 0.0; return LK_OK; }
+    if (!A) return fail(LK_ERR_INVALID, "lk_norm2_dense: null argument");
+    if (lda < m) return fail(LK_ERR_INVALID, "lk_norm2_dense: leading dimension below m = %d", m);
+    try {
+        *out = dtype == LK_C128 ? lk_expm::norm2(m, n, reinterpret_cast<const std::complex<double> *>(A), lda) : lk_expm::norm2(m, n, A, lda);
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_norm2_dense: no host memory for the work array of a %d x %d matrix", m, n);
     }
     return LK_OK;
 }
@@ -3666,6 +3822,118 @@ int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int 
     }
     if (err_est) *err_est = st.err;
     *info = st.err <= tol ? st.kp : -1;                          // :223-231
+    return LK_OK;
+}
+
+static int kexpm_block_impl(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t Bc, int jc0, int p, lk_basis_t X, double tau,
+                            double tol, int nk, int *info, double *err_est);
+
+// kexpm_mat (ExpmLib.fypp:234-363): see the header.  Host-synchronous, one block Arnoldi step per iteration.
+int lk_kexpm_block(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t Bc, int jc0, int p, lk_basis_t X, double tau, double tol,
+                   int nk, int *info, double *err_est) {
+    if (!A || !Bb || !Bc || !X || !info) return fail(LK_ERR_INVALID, "lk_kexpm_block: null argument");
+    if (p < 1) return fail(LK_ERR_INVALID, "lk_kexpm_block: the block needs at least one column (p = %d)", p);
+    if (jb0 < 0 || jb0 + p > Bb->ncols || jc0 < 0 || jc0 + p > Bc->ncols) return fail(LK_ERR_INVALID, "lk_kexpm_block: bad column range");
+    LKCHK(check_pair(Bb, X, "lk_kexpm_block(B, X)"));
+    LKCHK(check_pair(Bc, X, "lk_kexpm_block(C, X)"));
+    lk_context_t c = X->ctx;
+    if (A->ctx != c || A->dtype != X->dtype || A->n != X->n) return fail(LK_ERR_INVALID, "lk_kexpm_block: operator/vector mismatch");
+    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_kexpm_block: row-sharded contexts (nranks = %d) are not supported", c->nranks);
+    const int cmax = X->ncols < KMAX_WIDE ? X->ncols : KMAX_WIDE;
+    if (nk < 1 || (int64_t)p * ((int64_t)nk + 1) > cmax)
+        return fail(LK_ERR_INVALID, "lk_kexpm_block: p (nk + 1) = %lld columns outside [2 p, %d] (the workspace has %d columns; at most %d)",
+                    (long long)p * ((long long)nk + 1), cmax, X->ncols, KMAX_WIDE);
+    const int ncw = p * (nk + 1);                                // columns of X the call writes
+    for (int i = 0; i < p; ++i) {
+        if (overlaps(Bc->col(jc0 + i), X, 0, X->ncols)) return fail(LK_ERR_INVALID, "lk_kexpm_block: C has a column in the workspace X");
+        if (overlaps(Bc->col(jc0 + i), Bb, jb0, jb0 + p)) return fail(LK_ERR_INVALID, "lk_kexpm_block: C and B share a column");
+        if (overlaps(Bb->col(jb0 + i), X, 0, ncw)) return fail(LK_ERR_INVALID, "lk_kexpm_block: B has one of the workspace columns the call writes");
+    }
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    try {
+        return kexpm_block_impl(A, trans, Bb, jb0, Bc, jc0, p, X, tau, tol, nk, info, err_est);
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_kexpm_block: no host memory for the projected matrices of %d columns", p * (nk + 1));
+    }
+}
+
+// the evaluation itself: arguments validated, device selected and the lazy layer entered by lk_kexpm_block
+static int kexpm_block_impl(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t Bc, int jc0, int p, lk_basis_t X, double tau,
+                            double tol, int nk, int *info, double *err_est) {
+    const int ncw = p * (nk + 1);                                // columns of X the call writes
+    const int ED = X->ed();
+    const int dtype = X->dtype;
+    typedef std::complex<double> cplx;
+    *info = 0;
+
+    // Xwrk = B; qr(Xwrk, R, perm, info); permcols(R, invperm(perm))   :293, :297 (the qr's info is discarded there as well)
+    for (int i = 0; i < p; ++i) LKCHK(lk_vec_copy(X, i, Bb, jb0 + i));
+    std::vector<double> Rp((size_t)p * p * ED), R((size_t)p * p * ED);
+    std::vector<int> perm(p);
+    int qinfo = 0;
+    LKCHK(qr_pivot_impl(X, 0, p, Rp.data(), p, perm.data(), ATOL_DP, &qinfo));
+    double fro = 0.0;
+    for (int i = 0; i < p; ++i) {                                // column i of the pivoted factor belongs to column perm(i) of B
+        memcpy(R.data() + (size_t)(perm[i] - 1) * p * ED, Rp.data() + (size_t)i * p * ED, (size_t)p * ED * sizeof(double));
+        for (int e = 0; e < p * ED; ++e) fro += Rp[(size_t)i * p * ED + e] * Rp[(size_t)i * p * ED + e];
+    }
+    int kpp = p;
+    double err = 0.0;
+    if (fro == 0.0) {                                            // input is zero => output is zero   :299-302
+        for (int i = 0; i < p; ++i) LKCHK(lk_vec_zero(Bc, jc0 + i));
+    } else {
+        // initialize_krylov_subspace(X, Xwrk): qr_no_pivoting of the (already orthonormal) block   :304, utilities.fypp:44-46
+        {
+            bool flag = false;
+            qinfo = 0;
+            LKCHK(qr_columns_sync(X, 0, p, 0, false, 0.0, Rp.data(), p, ATOL_DP, &flag, &qinfo));
+        }
+        lk_basis_s Xv = basis_view(X, 0, ncw);                   // arnoldi sizes its factorisation by the basis it is given  arnoldi.fypp:26
+        const int64_t ldh = ncw;
+        std::vector<double> H((size_t)ldh * ldh * ED, 0.0), S((size_t)ldh * ldh * ED), E((size_t)ldh * ldh * ED), M((size_t)p * p * ED);
+        auto mul = [&](const double *Eblk, int rows, int64_t lde, double *out) {     // out (rows x p, packed) = Eblk(:rows, :p) R
+            for (int j = 0; j < p; ++j)
+                for (int i = 0; i < rows; ++i) {
+                    cplx s = 0.0;
+                    for (int l = 0; l < p; ++l) {
+                        const double *e = Eblk + ((size_t)l * lde + i) * ED, *r = R.data() + ((size_t)j * p + l) * ED;
+                        s += ED == 2 ? cplx(e[0], e[1]) * cplx(r[0], r[1]) : cplx(e[0] * r[0], 0.0);
+                    }
+                    out[((size_t)j * rows + i) * ED] = s.real();
+                    if (ED == 2) out[((size_t)j * rows + i) * ED + 1] = s.imag();
+                }
+        };
+        for (int k = 1; k <= nk; ++k) {                          // :306
+            const int kp = k * p;
+            int ainfo = 0;
+            if (p == 1) {                                        // :314 (blksize 1 is the vector factorisation, as in lk_arnoldi_block)
+                LKCHK(arnoldi_impl(A, &Xv, H.data(), ldh, k, k, ATOL_DP, trans, &ainfo, nullptr, 0, nullptr, nullptr));
+            } else {
+                int stop = 0;
+                LKCHK(arnoldi_block_step_sync(A, &Xv, H.data(), ldh, p, k, ATOL_DP, trans, &stop));
+                ainfo = stop ? kp : 0;
+            }
+            const bool breakdown = ainfo == kp;                  // :317-321
+            kpp = breakdown ? kp : kp + p;
+            for (int j = 0; j < kpp; ++j)
+                for (int i = 0; i < kpp * ED; ++i) S[(size_t)j * kpp * ED + i] = tau * H[(size_t)j * ldh * ED + i];
+            LKCHK(lk_expm_dense(dtype, kpp, S.data(), kpp, E.data(), kpp));                    // :324
+            if (breakdown) {
+                err = 0.0;                                       // :342-344
+            } else {
+                mul(E.data() + (size_t)kp * ED, p, kpp, M.data());                             // E(kp+1:kpp, :p) R   :346
+                LKCHK(lk_norm2_dense(dtype, p, p, M.data(), p, &err));
+            }
+            if (err <= tol) break;                               // :349
+        }
+        // C = X(:, :kpp) (E(:kpp, :p) R), once (:327-339 form it after every step)
+        std::vector<double> coef((size_t)kpp * p * ED);
+        mul(E.data(), kpp, kpp, coef.data());
+        LKCHK(lk_lincomb(&Xv, kpp, coef.data(), p, Bc, jc0));
+    }
+    if (err_est) *err_est = err;
+    *info = err <= tol ? kpp : -1;                               // :354-362
     return LK_OK;
 }
 

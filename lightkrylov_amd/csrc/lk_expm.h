@@ -1,5 +1,5 @@
 // lk_expm.h -- dense matrix exponential on the HOST (lk_expm_dense): what stdlib_linalg's `expm` is to the reference's
-// kexpm (src/Expm/ExpmLib.fypp:12, 207).  Plain C++: no device, no context, no LAPACK.  Included by lk_engine.hip; a stand-alone
+// kexpm (src/Expm/ExpmLib.fypp:12, 207) -- and, at the end, the spectral norm of a small matrix (lk_norm2_dense, :346).  Plain C++: no device, no context, no LAPACK.  Included by lk_engine.hip; a stand-alone
 // host program may include it too (it needs nothing but the public header).
 //
 // Scaling and squaring with the [13/13] Pade approximant (N. J. Higham, "The scaling and squaring method for the matrix
@@ -150,6 +150,80 @@ void expm(int n, const T *A, int64_t lda, T *E, int64_t lde) {
     }
     for (int j = 0; j < n; ++j)
         for (int i = 0; i < n; ++i) E[(size_t)j * lde + i] = R[(size_t)j * n + i];
+}
+
+// ||A||_2, the largest singular value of an m x n column-major matrix (leading dimension lda): what `norm(., 2)` is to kexpm_mat's
+// error estimate (ExpmLib.fypp:346).  One-sided Jacobi (Hestenes): plane rotations from the right make the columns of a packed copy
+// mutually orthogonal -- for the pair (p, q) with a = ||g_p||^2, b = ||g_q||^2, g = g_p^H g_q = |g| w: zeta = (b - a) / (2 |g|),
+// t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), c = 1 / sqrt(1 + t^2), s = c t, g_p <- c g_p - s conj(w) g_q, g_q <- s w g_p + c g_q --
+// until a whole sweep finds every pair orthogonal to machine precision; the singular values are then the column norms.  A wide matrix
+// is handled through its conjugate transpose (min(m, n) columns).  Small singular values come out to high RELATIVE accuracy, which a
+// route through A^H A would lose.  A non-finite entry gives NaN or Inf, never a loop without end (the sweeps are bounded).
+inline double conj1(double v) { return v; }
+inline std::complex<double> conj1(const std::complex<double> &v) { return std::conj(v); }
+inline double real1(double v) { return v; }
+inline double real1(const std::complex<double> &v) { return v.real(); }
+
+template <typename T>
+double norm2(int m, int n, const T *A, int64_t lda) {
+    if (m <= 0 || n <= 0) return 0.0;
+    const bool wide = n > m;
+    const int rows = wide ? n : m, cols = wide ? m : n;
+    std::vector<T> G((size_t)rows * cols);
+    for (int j = 0; j < n; ++j)
+        for (int i = 0; i < m; ++i) {
+            const T v = A[(size_t)j * lda + i];
+            if (wide) G[(size_t)i * rows + j] = conj1(v);
+            else G[(size_t)j * rows + i] = v;
+        }
+    const double eps = std::numeric_limits<double>::epsilon();
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p + 1 < cols; ++p)
+            for (int q = p + 1; q < cols; ++q) {
+                T *gp = G.data() + (size_t)p * rows, *gq = G.data() + (size_t)q * rows;
+                double a = 0.0, b = 0.0;
+                T g = T(0);
+                for (int i = 0; i < rows; ++i) {
+                    a += real1(conj1(gp[i]) * gp[i]);
+                    b += real1(conj1(gq[i]) * gq[i]);
+                    g += conj1(gp[i]) * gq[i];
+                }
+                const double ag = abs1(g);
+                if (!(ag > eps * std::sqrt(a) * std::sqrt(b))) continue;          // orthogonal already (or not a number: left alone)
+                rotated = true;
+                const T w = g / ag;
+                const double zeta = (b - a) / (2.0 * ag);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+                const T sw = s * w, swc = s * conj1(w);
+                for (int i = 0; i < rows; ++i) {
+                    const T u = gp[i], v = gq[i];
+                    gp[i] = c * u - swc * v;
+                    gq[i] = sw * u + c * v;
+                }
+            }
+        if (!rotated) break;
+    }
+    double best = 0.0;
+    bool anynan = false;
+    for (int j = 0; j < cols; ++j) {
+        const T *gj = G.data() + (size_t)j * rows;
+        double scale = 0.0;
+        for (int i = 0; i < rows; ++i) scale = std::fmax(scale, abs1(gj[i]));     // (fmax ignores a NaN: looked for below)
+        double s = 0.0;
+        bool nan = false;
+        for (int i = 0; i < rows; ++i) {
+            const double v = abs1(gj[i]);
+            if (v != v) nan = true;
+            if (scale > 0.0 && std::isfinite(scale)) s += (v / scale) * (v / scale);
+        }
+        double nj = (scale > 0.0 && std::isfinite(scale)) ? scale * std::sqrt(s) : scale;
+        if (nan) anynan = true;
+        if (nj > best) best = nj;
+    }
+    if (anynan) return std::numeric_limits<double>::quiet_NaN();
+    return best;
 }
 
 }  // namespace lk_expm

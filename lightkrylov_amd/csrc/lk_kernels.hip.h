@@ -3252,12 +3252,38 @@ __global__ __launch_bounds__(256) void k_axpby(double ar, double ai, const doubl
 }
 
 // copy(out, from): nd doubles, same shape as the beta == 0 branch above without the multiply (bit copy)
-__global__ __launch_bounds__(256) void k_copy(const double *__restrict__ x, double *__restrict__ y, int64_t nd, int nt) {
+// swap != 0 (block-uniform; swap_columns of qr_with_pivoting, qr.fypp:192-194, which is three copies through a fresh vector): x and y
+// EXCHANGE their contents in place -- two reads and two writes per element, no temporary.  Two streams, so one 16-byte access per
+// stream and lane in flight (the header's rule for axpby); x and y must be different columns.  The branch stands in front of the
+// copy's loops, which keep their code.
+__global__ __launch_bounds__(256) void k_copy(double *__restrict__ x, double *__restrict__ y, int64_t nd, int nt, int swap) {
     const int64_t nv = nd / 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (swap) {
+        v2d *xs = reinterpret_cast<v2d *>(x), *ys = reinterpret_cast<v2d *>(y);
+        if (nt) {
+            for (; i < nv; i += stride) {
+                const v2d a = __builtin_nontemporal_load(xs + i), b = __builtin_nontemporal_load(ys + i);
+                __builtin_nontemporal_store(a, ys + i);
+                __builtin_nontemporal_store(b, xs + i);
+            }
+        } else {
+            for (; i < nv; i += stride) {
+                const v2d a = xs[i], b = ys[i];
+                ys[i] = a;
+                xs[i] = b;
+            }
+        }
+        if ((nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            const double a = x[nd - 1], b = y[nd - 1];
+            y[nd - 1] = a;
+            x[nd - 1] = b;
+        }
+        return;
+    }
     const v2d *xv = reinterpret_cast<const v2d *>(x);
     v2d *yv = reinterpret_cast<v2d *>(y);
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (nt) {
         for (; i + stride < nv; i += 2 * stride) {
             const v2d a0 = __builtin_nontemporal_load(xv + i), a1 = __builtin_nontemporal_load(xv + i + stride);

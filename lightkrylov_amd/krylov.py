@@ -128,13 +128,105 @@ def _panel_columns(Q):
 
 
 # ------------------------------------------------------------------------------------------
-def qr(Q, R: np.ndarray, tol: float = atol_dp) -> int:
+def invperm(perm) -> np.ndarray:
+    """inv_perm(perm) = [1, 2, ..]: the inverse of a 1-based permutation, 1-based.  src/Krylov/utilities.fypp:21-27."""
+    perm = np.asarray(perm, dtype=np.intc)
+    inv = np.zeros(perm.size, dtype=np.intc)
+    inv[perm - 1] = np.arange(1, perm.size + 1, dtype=np.intc)
+    return inv
+
+
+def permcols(Q, perm):
+    """Q = Q(:, perm) for a 1-based permutation, in place: a 2-d array (permcols_array) or a basis of vectors (permcols_basis:
+    `copy(Q, Q(perm))` through temporaries).  src/Krylov/utilities.fypp:12-18."""
+    idx = np.asarray(perm, dtype=np.intc) - 1
+    if isinstance(Q, np.ndarray):
+        Q[...] = Q[:, idx]
+        return
+    tmp = []
+    for i in idx:
+        t = Q[int(i)].zeros_like()
+        copy(t, Q[int(i)])
+        tmp.append(t)
+    for j, t in enumerate(tmp):
+        copy(Q[j], t)
+
+
+def _swap_columns(Q, R, Rii, perm, i, j):
+    """swap_columns (qr.fypp:176-202) on user vector types: three copies through a temporary"""
+    wrk = Q[j].zeros_like()
+    copy(wrk, Q[j])                                                                 # :192-194
+    copy(Q[j], Q[i])
+    copy(Q[i], wrk)
+    Rii[[i, j]] = Rii[[j, i]]                                                       # :196
+    perm[[i, j]] = perm[[j, i]]                                                     # :197
+    n = min(i, j)
+    if n > 0:
+        R[:n, [i, j]] = R[:n, [j, i]]                                               # :199-201
+
+
+def _qr_with_pivoting(Q, R, perm, tol) -> int:
+    """qr_with_pivoting (qr.fypp:32-107) on the package's primitives, for vector types of the user's."""
+    p = len(Q)
+    info = 0
+    perm[:p] = np.arange(1, p + 1)                                                  # :49
+    Rii = np.array([Q[i].dot(Q[i]) for i in range(p)], dtype=R.dtype)               # :50
+    for j in range(p):
+        idx = int(np.argmax(np.abs(Rii)))                                           # :54 (first maximum)
+        if abs(Rii[idx]) < tol:                                                     # :55-66
+            for i in range(j, p):
+                Q[i].rand()
+                if i > 0:
+                    double_gram_schmidt_step(Q[i], Q[:i], if_chk_orthonormal=False)
+                Q[i].scal(1.0 / Q[i].norm())
+            return j + 1
+        if idx != j:
+            _swap_columns(Q, R, Rii, perm, j, idx)                                  # :68
+        beta = Q[j].norm()                                                          # :71
+        if np.isnan(beta):
+            raise FloatingPointError("|beta| = NaN detected! Abort")               # :73-77
+        if abs(beta) < tol:                                                         # :79-85
+            info = j + 1
+            R[j, j] = 0
+            Q[j].rand()
+            if j > 0:
+                double_gram_schmidt_step(Q[j], Q[:j], if_chk_orthonormal=False)
+            beta = Q[j].norm()
+        else:
+            R[j, j] = beta                                                          # :87
+        Q[j].scal(1.0 / beta)                                                       # :90
+        for i in range(j + 1, p):                                                   # :93-97
+            h = Q[j].dot(Q[i])
+            Q[i].axpby(-h, Q[j], 1.0)
+            R[j, i] = h
+        Rii[j] = 0                                                                  # :100-103
+        Rii[j + 1:] -= R[j, j + 1:p] ** 2
+    return info
+
+
+def qr(Q, R: np.ndarray, tol: float = atol_dp, perm: np.ndarray | None = None) -> int:
     """qr_no_pivoting: in-place DGS-based QR of the basis Q, R upper triangular.
-    src/Krylov/qr.fypp:116-167.  Returns info (index of the first colinear column, 1-based)."""
+    src/Krylov/qr.fypp:116-167.  Returns info (index of the first colinear column, 1-based).
+    With `perm` (an int array of len(Q) entries, filled with the 1-based column ordering): qr_with_pivoting, :32-107 -- Q R equals the
+    input's columns `perm`; info = the column at which the remaining ones were found to be (numerically) zero and re-drawn.  Columns
+    of one device panel run inside the engine (lk_qr_pivot); other vector types on the package's primitives."""
     p = len(Q)
     if R.ndim != 2 or R.shape[0] < p or R.shape[1] < p:
         raise ValueError(f"qr: R has shape {R.shape}, the factor of {p} columns needs at least ({p}, {p})")
     R[...] = 0                                                                      # :125 (all of R, also beyond p x p)
+    if perm is not None:
+        if not isinstance(perm, np.ndarray) or perm.dtype.kind != "i" or perm.ndim != 1 or perm.size != p:
+            raise ValueError(f"qr: perm must be an integer array of {p} entries")
+        cols = _panel_columns(Q)
+        if cols is not None and R.flags.f_contiguous and R.dtype == cols[0].dtype:
+            B, j0, p = cols
+            cinfo = C.c_int()
+            cperm = np.zeros(p, dtype=np.intc)
+            _capi.check(B._lib.lk_qr_pivot(B._h, j0, p, R.ctypes.data_as(_DP), R.shape[0], cperm.ctypes.data_as(C.POINTER(C.c_int)),
+                                           float(tol), C.byref(cinfo)))
+            perm[...] = cperm
+            return cinfo.value
+        return _qr_with_pivoting(Q, R, perm, tol)
     # columns of ONE device panel: the whole factorisation inside the engine (lk_qr)
     cols = _panel_columns(Q)
     if cols is not None and R.flags.f_contiguous and R.dtype == cols[0].dtype:

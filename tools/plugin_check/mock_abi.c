@@ -276,6 +276,17 @@ int lk_kexpm(void *A, int trans, void *Bb, int jb, void *Bc, int jc, void *X, do
     (void)A; (void)trans; (void)Bb; (void)jb; (void)Bc; (void)jc; (void)X; (void)tau; (void)tol; (void)kdim; (void)info; (void)err_est;
     return fail("lk_kexpm is not in the mock");
 }
+int lk_norm2_dense(int dtype, int m, int n, const double *A, int64_t lda, double *out) {
+    (void)dtype; (void)m; (void)n; (void)A; (void)lda; (void)out; return fail("lk_norm2_dense is not in the mock");
+}
+int lk_qr_pivot(void *Q, int j0, int p, double *R, int64_t ldr, int *perm, double tol, int *info) {
+    (void)Q; (void)j0; (void)p; (void)R; (void)ldr; (void)perm; (void)tol; (void)info; return fail("lk_qr_pivot is not in the mock");
+}
+int lk_kexpm_block(void *A, int trans, void *Bb, int jb0, void *Bc, int jc0, int p, void *X, double tau, double tol, int nk, int *info,
+                   double *err_est) {
+    (void)A; (void)trans; (void)Bb; (void)jb0; (void)Bc; (void)jc0; (void)p; (void)X; (void)tau; (void)tol; (void)nk; (void)info; (void)err_est;
+    return fail("lk_kexpm_block is not in the mock");
+}
 int lk_comm_get_unique_id(void *id) { memset(id, 0, 128); return LK_OK; }
 int lk_comm_init_rank(mock_ctx *c, int nranks, int rank, const void *id) { (void)c; (void)rank; (void)id; return nranks == 1 ? LK_OK : fail("no collective in the mock"); }
 int lk_comm_info(mock_ctx *c, int *nranks, int *rank) { (void)c; if (nranks) *nranks = 1; if (rank) *rank = 0; return LK_OK; }
