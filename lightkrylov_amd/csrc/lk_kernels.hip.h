@@ -170,14 +170,13 @@ enum { ROWOP_NONE = 0, ROWOP_LIN = 1, ROWOP_DIAG = 2 };
 // is off inside (the complex products are written out with the fused multiply-adds k_diag compiles to), and the result passes
 // through an empty asm so that no later pass can fold the multiplication into its consumer.
 // `dout` (real kind): receives d of the lane's two rows, for a sweep that applies the operator a second time (rowop_apply).
+// rowop_form: the product from rows already loaded -- `b` of x, `a` of d (read by the complex kind and by ROWOP_DIAG only) -- so that a sweep
+// which fetches its next tile ahead of time (panel_sweep, PF) rounds y exactly as rowop_y does.
 template <bool CPLX>
-__device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict__ x, int64_t r, int64_t n, bool full, v2d *dout = nullptr) {
+__device__ __forceinline__ v2d rowop_form(const RowOp &op, v2d b, v2d a, int64_t r, int64_t n, bool full, v2d *dout = nullptr) {
 #pragma clang fp contract(off)
-    auto ld = [&](const double *__restrict__ p) -> v2d { return load_y<CPLX>(p, r, n, full); };
-    const v2d b = ld(x);
     v2d yv;
     if constexpr (CPLX) {
-        const v2d a = ld(op.d);
         yv = op.conj ? diag_cmulconj(a, b) : diag_cmul(a, b);
     } else if (op.kind == ROWOP_LIN) {
         const double g = (double)(op.row0 + r);
@@ -189,13 +188,20 @@ __device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict
             if (r + 1 >= n) yv.y = 0.0;
         }
     } else {
-        const v2d dv = ld(op.d);
+        const v2d dv = a;
         yv = dv * b;
         if (dout) *dout = dv;
     }
     asm("" : "+v"(yv.x));
     asm("" : "+v"(yv.y));
     return yv;
+}
+template <bool CPLX>
+__device__ __forceinline__ v2d rowop_y(const RowOp &op, const double *__restrict__ x, int64_t r, int64_t n, bool full, v2d *dout = nullptr) {
+    const v2d b = load_y<CPLX>(x, r, n, full);
+    v2d a = v2d{0.0, 0.0};
+    if (CPLX || op.kind != ROWOP_LIN) a = load_y<CPLX>(op.d, r, n, full);
+    return rowop_form<CPLX>(op, b, a, r, n, full, dout);
 }
 // w = D v for rows whose d the sweep already holds (real kind): one rounded product per row, as rowop_y forms y
 __device__ __forceinline__ v2d rowop_apply(v2d dv, v2d v) {
@@ -334,6 +340,17 @@ __device__ __forceinline__ void store_rows(double *__restrict__ y, int64_t r, in
 // it always was), slot k+1 = sum y'' w, slot k+2 = sum |w|^2.  With beta = ||y''|| the next step's vector is y_next = w / beta and its
 // last basis column y'' / beta, so k_scal turns these sums into h1 and ||y_next||^2 of step k+1 by k + 2 divisions.  Both coefficient
 // sets live in LDS and are read per use, so that the tile and its accumulators keep the registers.
+//
+// PF (the real kind's sweep 2 <false, 16, 8, true, true, false, 1, 1> and the look-ahead sweep <false, 16, 8, true, false, false, 1, 1>): one
+// block per CU holds its tile in registers across the exchange barrier, so between the last byte of a tile and the first of the next the CU
+// had nothing in flight.  A block that walks at least two tiles now fetches tile t + 1 while it works on tile t: every wave sends its nc live
+// columns of the next full tile into a private LDS region by LDS-DMA (no registers: a second register tile does not fit), together with
+// the rows of y's source, of d, and -- look-ahead sweep, whose LDS holds 15 columns per wave beside its exchange buffers -- its 16th column
+// in a few spare registers.  The top of the next iteration waits for all of it, reads the region into the tile's registers and sends the
+// DMA for the tile after that at once.  Inside the span where it is in flight the exchange meets at a raw s_barrier behind an LDS-only wait
+// (__syncthreads() would drain the prefetch) and no ordinary load has its first use.  The block's last tile if it is ragged, and a block's
+// only tile, take the plain loads as before; slot order, exchange order, accumulator chains and the tile-to-block mapping are untouched,
+// so every output keeps its bits.  168 / 216 VGPRs, no scratch, 148 544 / 158 912 bytes of LDS.
 template <bool CPLX, int KC, int NW, bool UPDATE, bool DOT, bool TWO, int SC = 1, int G = 1>
 __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 : 1) void panel_sweep(const double *__restrict__ X, int64_t ldx, int k,
                                                         double *__restrict__ y, int64_t n,
@@ -356,6 +373,10 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     constexpr int NU = T2 ? 2 : 1;
     constexpr bool BIG = KC > 16;        // wide register tile: scalar-base addressing (SC = 1), slim accumulators
     constexpr bool FUSE = rowop_fusable<CPLX, KC>;
+    // PF: sweep 2 and the look-ahead sweep of the real kind fetch the block's NEXT tile while they work on this one (header comment).
+    // STG columns of a wave go through its private LDS region; the look-ahead sweep's LDS holds 15, its 16th waits in four registers.
+    constexpr bool PF = !CPLX && KC == 16 && NW == 8 && UPDATE && !TWO && SC == 1 && G == 1;
+    constexpr int STG = LA ? 15 : 16;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -373,6 +394,7 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     __shared__ v2d u_lds[UPDATE ? 2 * NU * NW * 64 : 1];
     constexpr int SLOTS = KC * ED + (LA ? 3 : 1);      // a wave's dots, the norm, and the look-ahead's two sums
     __shared__ double red_lds[NW * SC * SLOTS];
+    __shared__ v2d stage_lds[PF ? NW * STG * 64 : 1];  // PF: wave w's columns of the next tile, column jj at [(w * STG + jj) * 64 + lane]
 
     // projection coefficients of this wave's columns: wave-uniform (scalar registers) for SC = 1.  With the lane split they
     // differ from lane group to lane group and would take 2-4 VGPRs per column and coefficient set on top of the tile
@@ -454,7 +476,45 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
     const int64_t tbase = xmap ? (int64_t)(blockIdx.x & 7) * chunk : 0;
     const int64_t tend = xmap ? (tbase + chunk < ntiles ? tbase + chunk : ntiles) : ntiles;
     const int64_t tstep = xmap ? gridDim.x >> 3 : gridDim.x;
-    for (int64_t t = tbase + (xmap ? blockIdx.x >> 3 : blockIdx.x); t < tend; t += tstep) {
+    const int64_t tfirst = tbase + (xmap ? blockIdx.x >> 3 : blockIdx.x);
+
+    // PF: tile `tn` (a full one) on its way while the block works on the tile before it.  Each wave's nc live columns go straight into its
+    // LDS region by LDS-DMA (one instruction = the 64 lanes' 16 bytes of one column, 1 KB at a wave-uniform base; no registers); column STG,
+    // y's source (y, or column k-1 under a row operator) and d of an explicit diagonal wait in xpre / ypre / dpre.  Nothing of this is
+    // touched before the top of the next iteration, which waits for all of it: every lane reads back the 16 bytes it fetched itself, so
+    // the region needs no barrier and no padding.
+    v2d xpre = v2d{0.0, 0.0}, ypre = v2d{0.0, 0.0}, dpre = v2d{0.0, 0.0};
+    bool staged = false;                               // block-uniform: the tile the loop is about to take was prefetched
+    auto prefetch = [&](int64_t tn) {
+        if constexpr (PF) {
+            const int64_t rn = tn * tile_rows + roff;
+            const double *src = Xw + rn;
+            // The DMA is written in assembly (M0 = LDS address of the column's 1 KB; nt: the panel is read once).  Issued through the builtin,
+            // the compiler knows of an LDS write in flight and guards LDS reads it cannot tell apart from it with vmcnt(0): it did so in
+            // front of the look-ahead sweep's exchange reads, which drained the prefetch in the middle of every tile.  Hidden from it, the
+            // only wait these loads ever meet is the vmcnt(0) at the top of the next tile (its own counted waits can only come out stricter).
+            const unsigned dst = (unsigned)(uintptr_t)(reinterpret_cast<char *>(stage_lds) + wave * (STG * 1024));
+#pragma unroll
+            for (int jj = 0; jj < STG; ++jj)
+                if (jj < nc) {
+                    unsigned m0save;               // (M0 is the compiler's own: handed back as it was)
+                    asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %1, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off nt\n\ts_mov_b32 m0, %0"
+                                 : "=&s"(m0save) : "s"(dst), "v"(src + jj * colstride), "n"(jj * 1024) : "memory", "scc");
+                }
+            if constexpr (STG < KC)
+                if (nc > STG) xpre = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(src + STG * colstride));
+            ypre = *reinterpret_cast<const v2d *>((rop.kind != ROWOP_NONE ? xk : y) + rn);
+            if (rop.kind == ROWOP_DIAG) dpre = *reinterpret_cast<const v2d *>(rop.d + rn);
+        }
+    };
+    if constexpr (PF) {
+        static_assert(STG >= KC - 1, "one column in registers at the most");
+        if (tfirst + tstep < tend && (tfirst + 1) * tile_rows <= n) {    // a block of one tile keeps the plain loads
+            prefetch(tfirst);
+            staged = true;
+        }
+    }
+    for (int64_t t = tfirst; t < tend; t += tstep) {
         const int64_t r = t * tile_rows + roff;        // first row of this lane
         const bool full = (t + 1) * tile_rows <= n;   // block-uniform
         v2d xv[KC];
@@ -462,7 +522,47 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
         v2d dv = v2d{0.0, 0.0};                        // look-ahead: d of the lane's rows, kept from forming y
         v2d *const dout = LA ? &dv : nullptr;
         if constexpr (LA) asm volatile("" : "+s"(hb));
-        if constexpr (G > 1) {
+        if (PF && staged) {
+            // everything outstanding has landed -> the region into registers -> LDS reads done -> the next tile into the same region.
+            // The reads and the wait for them are ONE asm statement: the compiler does not count an asm read, so nothing of its own
+            // (a copy, a split live range) may come between a read and the wait.  All STG slots are read, the empty ones too (whatever
+            // the region holds there, never used: the select below is wave-uniform).
+            if constexpr (PF) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                const unsigned a = (unsigned)(uintptr_t)(reinterpret_cast<char *>(stage_lds) + wave * (STG * 1024) + lane * 16);
+                v2d s[16];
+#define LK_STAGE_READS_15                                                                                                                \
+    "ds_read_b128 %0, %[a]\n\tds_read_b128 %1, %[a] offset:1024\n\tds_read_b128 %2, %[a] offset:2048\n\tds_read_b128 %3, %[a] offset:3072\n\t"          \
+    "ds_read_b128 %4, %[a] offset:4096\n\tds_read_b128 %5, %[a] offset:5120\n\tds_read_b128 %6, %[a] offset:6144\n\tds_read_b128 %7, %[a] offset:7168\n\t" \
+    "ds_read_b128 %8, %[a] offset:8192\n\tds_read_b128 %9, %[a] offset:9216\n\tds_read_b128 %10, %[a] offset:10240\n\t"                                 \
+    "ds_read_b128 %11, %[a] offset:11264\n\tds_read_b128 %12, %[a] offset:12288\n\tds_read_b128 %13, %[a] offset:13312\n\t"                             \
+    "ds_read_b128 %14, %[a] offset:14336\n\t"
+                if constexpr (STG == 16)
+                    asm volatile(LK_STAGE_READS_15 "ds_read_b128 %15, %[a] offset:15360\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]), "=&v"(s[6]), "=&v"(s[7]), "=&v"(s[8]),
+                                   "=&v"(s[9]), "=&v"(s[10]), "=&v"(s[11]), "=&v"(s[12]), "=&v"(s[13]), "=&v"(s[14]), "=&v"(s[15])
+                                 : [a] "v"(a) : "memory");
+                else
+                    asm volatile(LK_STAGE_READS_15 "s_waitcnt lgkmcnt(0)"
+                                 : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3]), "=&v"(s[4]), "=&v"(s[5]), "=&v"(s[6]), "=&v"(s[7]), "=&v"(s[8]),
+                                   "=&v"(s[9]), "=&v"(s[10]), "=&v"(s[11]), "=&v"(s[12]), "=&v"(s[13]), "=&v"(s[14])
+                                 : [a] "v"(a) : "memory");
+#undef LK_STAGE_READS_15
+                static_assert(STG == 15 || STG == 16, "the read-back is written out for these two");
+#pragma unroll
+                for (int jj = 0; jj < KC; ++jj) {
+                    if (jj < STG) xv[jj] = jj < nc ? s[jj] : v2d{0.0, 0.0};
+                    else xv[jj] = nc > STG ? xpre : v2d{0.0, 0.0};
+                }
+            }
+            const v2d yb = ypre, db = dpre;
+            const int64_t tn = t + tstep;
+            staged = tn < tend && (tn + 1) * tile_rows <= n;
+            if (staged) prefetch(tn);
+            yv = yb;
+            if constexpr (FUSE)
+                if (rop.kind != ROWOP_NONE) yv = rowop_form<CPLX>(rop, yb, db, r, n, true, dout);
+        } else if constexpr (G > 1) {
             // slot g * KCG + j <- column c0 + g * kcw + j (j < kcw, column < k); the other slots hold zeros
             yv = load_y_op<CPLX, FUSE>(rop, y, xk, r, n, full);
 #pragma unroll
@@ -546,7 +646,12 @@ __global__ __launch_bounds__(NW * 64, (CPLX && KC == 8 && NW == 16 && TWO) ? 8 :
                 v2d *ub = u_lds + buf * (NU * NW * 64);
                 ub[wave * 64 + lane] = u;
                 if constexpr (T2) ub[NW * 64 + wave * 64 + lane] = u2;
-                __syncthreads();
+                if constexpr (PF) {
+                    // a raw barrier behind an LDS-only wait: __syncthreads() would wait for the prefetch as well (vmcnt(0))
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                } else __syncthreads();
                 v2d s = v2d{0.0, 0.0}, s2 = v2d{0.0, 0.0};
                 for (int w = 0; w < WC; ++w) s += ub[(wr * WC + w) * 64 + lane];
                 if constexpr (T2)
