@@ -62,6 +62,7 @@ module lightkrylov_gpu
     public :: gpu_lanczos_rdp, gpu_lanczos_cdp, gpu_bidiag_rdp, gpu_bidiag_cdp, gpu_qr_rdp, gpu_qr_cdp
     public :: gpu_kexpm_rdp, gpu_kexpm_cdp
     public :: gpu_qr_pivot_rdp, gpu_qr_pivot_cdp, gpu_kexpm_block_rdp, gpu_kexpm_block_cdp
+    public :: gpu_gmres_rdp, gpu_gmres_cdp, gpu_linop_compose, gpu_residual_rdp, gpu_residual_cdp
 
     type(c_ptr), save :: ctx = c_null_ptr
     integer(c_int64_t), save :: part_row0 = 0          ! first global row of this rank's block (lk_gpu_set_partition)
@@ -1073,5 +1074,93 @@ contains
         integer, optional, intent(in) :: kdim
         real(dp), optional, intent(out) :: err_est
         call gpu_kexpm_block_rdp(Bc, jc0, op, Bb, jb0, p, X, tau, tol, info, trans, kdim, err_est)
+    end subroutine
+
+    !> The product op_a(A) op_b(B) of two engine operators as an engine operator (lk_linop_compose_create): its matvec is the two
+    !> factors' through one scratch vector, its rmatvec the adjoint product.  A and B are not owned and must outlive op; release op with
+    !> lk_linop_destroy.  A user's abstract_linop that chains two others (src/AbstractTypes/AbstractLinops.fypp:58-87), without the host.
+    subroutine gpu_linop_compose(op, A, B, transA, transB)
+        type(c_ptr), intent(out) :: op
+        type(c_ptr), intent(in) :: A, B
+        logical, optional, intent(in) :: transA, transB
+        integer(c_int) :: ta, tb
+        ta = 0; if (present(transA)) ta = merge(1, 0, transA)
+        tb = 0; if (present(transB)) tb = merge(1, 0, transB)
+        call chk(lk_linop_compose_create(A, ta, B, tb, op), 'gpu_linop_compose')
+    end subroutine
+
+    !> r = b - op(A) x and ||r|| (src/IterativeSolvers/GMRES/gmres.fypp:134-142) as ONE engine call (lk_linop_residual): column jr
+    !> (0-based) of the panel Br, from column jx of Bx and column jb of Bb.  Without `nrm` the sum stays on the device and the call
+    !> does not synchronise.  The handles carry the kind: the two names exist for symmetry with the other wrappers.
+    subroutine gpu_residual_rdp(Br, jr, op, Bx, jx, Bb, jb, nrm, trans)
+        type(c_ptr), intent(in) :: Br, op, Bx, Bb
+        integer, intent(in) :: jr, jx, jb
+        real(dp), optional, intent(out), target :: nrm
+        logical, optional, intent(in) :: trans
+        integer(c_int) :: tr
+        type(c_ptr) :: pn
+        tr = 0; if (present(trans)) tr = merge(1, 0, trans)
+        pn = c_null_ptr; if (present(nrm)) pn = c_loc(nrm)
+        call chk(lk_linop_residual(op, tr, Bx, int(jx, c_int), Bb, int(jb, c_int), Br, int(jr, c_int), pn), 'gpu_residual')
+    end subroutine
+
+    subroutine gpu_residual_cdp(Br, jr, op, Bx, jx, Bb, jb, nrm, trans)
+        type(c_ptr), intent(in) :: Br, op, Bx, Bb
+        integer, intent(in) :: jr, jx, jb
+        real(dp), optional, intent(out), target :: nrm
+        logical, optional, intent(in) :: trans
+        call gpu_residual_rdp(Br, jr, op, Bx, jx, Bb, jb, nrm, trans)
+    end subroutine
+
+    !> gmres (src/IterativeSolvers/GMRES/gmres.fypp:65-255) as ONE engine call (lk_gmres): solves op(A) x = b for column jx (0-based) of
+    !> the panel Bx (initial guess, overwritten) with b = column jb of Bb.  V: the caller's workspace panel of at least kdim + 1 columns,
+    !> kdim + 2 with a preconditioner.  precond: a RIGHT preconditioner given as an engine operator (e.g. a diagonal operator holding
+    !> 1 / diag(A)); absent = none.  rtol, atol, kdim and maxiter default to the reference's (rtol_dp, atol_dp, 30, 10).  info = +n_iter
+    !> converged, -n_iter not.  res (optional) receives the residual history up to its size, nres its full length.
+    subroutine gpu_gmres_rdp(op, Bb, jb, Bx, jx, V, info, rtol, atol, precond, kdim, maxiter, trans, res, nres, n_inner, n_outer)
+        type(c_ptr), intent(in) :: op, Bb, Bx, V
+        integer, intent(in) :: jb, jx
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: rtol, atol
+        type(c_ptr), optional, intent(in) :: precond
+        integer, optional, intent(in) :: kdim, maxiter
+        logical, optional, intent(in) :: trans
+        real(dp), optional, intent(out) :: res(:)
+        integer, optional, intent(out) :: nres, n_inner, n_outer
+        integer(c_int) :: cinfo, tr, kd, mi, ni, no
+        integer(c_int64_t) :: nr
+        real(c_double) :: rt, at
+        real(c_double) :: none(1)
+        type(c_ptr) :: M
+        tr = 0; if (present(trans)) tr = merge(1, 0, trans)
+        kd = 30; if (present(kdim)) kd = kdim                                 ! gmres_dp_opts, IterativeSolvers.fypp:141-151
+        mi = 10; if (present(maxiter)) mi = maxiter
+        at = 10.0_dp**(-precision(1.0_dp)); if (present(atol)) at = atol      ! atol_dp, Constants.f90:35
+        rt = sqrt(10.0_dp**(-precision(1.0_dp))); if (present(rtol)) rt = rtol   ! rtol_dp = sqrt(atol_dp), Constants.f90:37
+        M = c_null_ptr; if (present(precond)) M = precond
+        if (present(res)) then
+            call chk(lk_gmres(op, tr, M, Bb, int(jb, c_int), Bx, int(jx, c_int), V, rt, at, kd, mi, res, int(size(res), c_int64_t), &
+                              nr, ni, no, cinfo), 'gpu_gmres')
+        else
+            call chk(lk_gmres(op, tr, M, Bb, int(jb, c_int), Bx, int(jx, c_int), V, rt, at, kd, mi, none, 0_c_int64_t, &
+                              nr, ni, no, cinfo), 'gpu_gmres')
+        end if
+        info = cinfo
+        if (present(nres)) nres = int(nr)
+        if (present(n_inner)) n_inner = ni
+        if (present(n_outer)) n_outer = no
+    end subroutine
+
+    subroutine gpu_gmres_cdp(op, Bb, jb, Bx, jx, V, info, rtol, atol, precond, kdim, maxiter, trans, res, nres, n_inner, n_outer)
+        type(c_ptr), intent(in) :: op, Bb, Bx, V
+        integer, intent(in) :: jb, jx
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: rtol, atol
+        type(c_ptr), optional, intent(in) :: precond
+        integer, optional, intent(in) :: kdim, maxiter
+        logical, optional, intent(in) :: trans
+        real(dp), optional, intent(out) :: res(:)
+        integer, optional, intent(out) :: nres, n_inner, n_outer
+        call gpu_gmres_rdp(op, Bb, jb, Bx, jx, V, info, rtol, atol, precond, kdim, maxiter, trans, res, nres, n_inner, n_outer)
     end subroutine
 end module lightkrylov_gpu

@@ -542,6 +542,38 @@ module lightkrylov_hip_c
             real(c_double), intent(out) :: err_est
             integer(c_int) :: rc
         end function
+        !> product of two engine operators (AbstractLinops.fypp:58-87): LK_OP_N applies op_a(A) op_b(B) x, LK_OP_H the adjoint.  A and B
+        !> are not owned and must outlive op.
+        function lk_linop_compose_create(A, transA, B, transB, op) bind(C, name="lk_linop_compose_create") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: A, B
+            integer(c_int), value :: transA, transB
+            type(c_ptr), intent(out) :: op
+            integer(c_int) :: rc
+        end function
+        !> r = b - op(A) x and its norm in one pass behind the product (gmres.fypp:134-142): column jr of Br, from column jx of Bx and
+        !> column jb of Bb.  nrm: c_loc of a real(c_double), or c_null_ptr -- the sum then stays on the device and nothing synchronises
+        function lk_linop_residual(A, trans, Bx, jx, Bb, jb, Br, jr, nrm) bind(C, name="lk_linop_residual") result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr), value :: A, Bx, Bb, Br, nrm
+            integer(c_int), value :: trans, jx, jb, jr
+            integer(c_int) :: rc
+        end function
+        !> restarted GMRES(kdim) as one call (gmres.fypp:65-255): op(A) x = b, x = column jx of Bx (initial guess, overwritten), b =
+        !> column jb of Bb; M = c_null_ptr or a right preconditioner (an engine operator); V = workspace of >= kdim + 1 columns (kdim + 2
+        !> with M).  res: res_cap entries of the residual history at most, nres its full length
+        function lk_gmres(A, trans, M, Bb, jb, Bx, jx, V, rtol, atol, kdim, maxiter, res, res_cap, nres, n_inner, n_outer, info) &
+            bind(C, name="lk_gmres") result(rc)
+            import :: c_int, c_ptr, c_double, c_int64_t
+            type(c_ptr), value :: A, M, Bb, Bx, V
+            integer(c_int), value :: trans, jb, jx, kdim, maxiter
+            real(c_double), value :: rtol, atol
+            real(c_double), intent(inout) :: res(*)
+            integer(c_int64_t), value :: res_cap
+            integer(c_int64_t), intent(out) :: nres
+            integer(c_int), intent(out) :: n_inner, n_outer, info
+            integer(c_int) :: rc
+        end function
     end interface
 
 contains

@@ -400,9 +400,27 @@ int lk_linop_gl_create(lk_context_t ctx, int64_t n, double dx, double tau, int n
 int lk_linop_gl_create_sharded(lk_context_t ctx, int64_t n_global, int64_t row0, int64_t n_local, double dx,
                                double tau, int nsub, const double *nu, const double *gamma, double mu_c,
                                double mu2, lk_linop_t *op);
+/* Product of two engine operators: LK_OP_N applies y = op_a(A) op_b(B) x, LK_OP_H the adjoint op_b(B)^H op_a(A)^H x (transA / transB:
+ * LK_OP_N or LK_OP_H) -- what a user's abstract_linop whose matvec chains two others does (AbstractLinops.fypp:58-87), and how a fixed
+ * right preconditioner enters an Arnoldi batch without a host round trip (gmres.fypp:155-165: V(k+1) = A M V(k)).  The operator owns ONE
+ * scratch vector, allocated here; its application enqueues the two factors' through it -- the same kernels, the same bits as two
+ * lk_linop_apply calls through a temporary -- so it works on a row-sharded context whenever both factors do.  It does NOT own A or B:
+ * both must outlive it.  No row-local form (the "fuse_rowop" schedules do not apply); its "matvec" bytes are the factors' plus the
+ * scratch written and read.  lk_arnoldi, lk_kexpm and eigs on a product of engine operators run fused through it.
+ * LK_ERR_INVALID: a null argument; factors of different context, kind or size. */
+int lk_linop_compose_create(lk_linop_t A, int transA, lk_linop_t B, int transB, lk_linop_t *op);
 int lk_linop_destroy(lk_linop_t op);
 /* apply_matvec / apply_rmatvec: y(:, jy) = op(A) x(:, jx).  AbstractLinops.fypp:391-424 */
 int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t By, int jy);
+/* r = b - op(A) x and ||r||: gmres.fypp:134-142 (and :205-214; CG.fypp:108-109), which spell it matvec, sub, chsgn, norm.  The
+ * operator's product is enqueued into r, then ONE kernel (k_axpby's residual branch) forms r <- b - r in place and the per-block sums
+ * of |r|^2 in the same pass
+ * (finished in a fixed order, no floating-point atomics; all-reduced over the ranks of a row-sharded context): one read-write pass
+ * where sub, chsgn and norm take two and a read pass.  r is bit for bit what the three calls leave; the norm agrees to rounding
+ * (another summation order).  nrm may be NULL: the sum then stays on the device and the call does not synchronise.
+ * LK_ERR_INVALID: r the same column as x or b; operator and vectors of different shape, kind or context.  A NaN is no error here:
+ * it comes back as the norm. */
+int lk_linop_residual(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_basis_t Bb, int jb, lk_basis_t Br, int jr, double *nrm);
 
 /* ---- the caller of the path: Arnoldi --------------------------------------------------
  * arnoldi(A, X, H, info, kstart, kend, tol, transpose) with blksize = 1 (lk_arnoldi_block: any blksize).
@@ -539,6 +557,38 @@ int lk_qr_pivot(lk_basis_t Q, int j0, int p, double *R, int64_t ldr, int *perm, 
  * context (nranks > 1). */
 int lk_kexpm_block(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t Bc, int jc0, int p, lk_basis_t X, double tau, double tol,
                    int nk, int *info, double *err_est);
+
+/* ---- restarted GMRES(kdim) as one call ----------------------------------------------------------------------------------
+ * gmres(A, b, x, info, rtol, atol, preconditioner, options, transpose, meta): src/IterativeSolvers/GMRES/gmres.fypp:65-255.
+ * Solves op(A) x = b; x = column jx of Bx is the initial guess and is overwritten, b = column jb of Bb is read only.  M: NULL, or a
+ * RIGHT preconditioner given as an engine operator, always applied as LK_OP_N: the step is V(k+1) = op(A) M V(k) (:155-165) -- one
+ * Arnoldi batch on the product of the two operators, see lk_linop_compose_create -- and the update x += M (V y) (:201-202).  The
+ * reference hands k, beta and tol to the preconditioner's apply; a fixed operator has no use for them.  (The flexible variant,
+ * fgmres.fypp, with a fixed operator IS this call; a preconditioner that varies needs a host callback per step and is not provided.)
+ * V: workspace of the CALLER, as in lk_kexpm: >= kdim + 1 columns, >= kdim + 2 with M (the extra column is the scratch vector of the
+ * product operator, which lives on the call's stack); 2 <= kdim <= 512.  No device memory is allocated beyond the context's grow-once
+ * workspaces.  options%kdim and %maxiter are the arguments of those names: at most maxiter + 1 cycles (:131).
+ * Schedule.  ONE host synchronisation at entry (||b|| for tol = atol + rtol ||b||, :106, and ||x|| for the test at :134), then ONE PER
+ * CYCLE plus those of the Arnoldi batch's deliveries.  A cycle starts with lk_linop_residual into V(:, 0), the sum left on the device,
+ * where the normalisation reads it (:134-143); beta reaches the host with the first delivery of the batch.  The inner steps are one
+ * Arnoldi batch with tolerance tol, delivered step by step as in lk_arnoldi_segments: the host applies the Givens rotations and appends
+ * |e(k+1)| to the history while the device runs ahead, and stops the batch at |e(k+1)| < tol (:178-195; the steps run ahead touch only
+ * columns the update does not read).  A batch that ends on H(k+1, k) <= tol with the residual still >= tol is followed by the remaining
+ * steps one by one, the new vector left unscaled, as the reference does (:171-172; lk_arnoldi has normalised the vector of the step it
+ * stopped at, which is undone to rounding; a vector below atol_dp it has REPLACED by a normalised random one, qr.fypp:146-162, and
+ * the call goes on with that one where the reference keeps the tiny vector -- reachable only with tol < atol_dp = 1e-15).  The triangular solve (:199-200) is back
+ * substitution on the host -- a zero pivot is LK_ERR_INVALID "TRTRS failed" --, dx = V(:, :k) y goes to V(:, kdim), M dx to V(:, 0),
+ * x += dx.  The cycle ends with lk_linop_residual into V(:, 0) and its norm (:205-214); when the solve goes on, the NEXT cycle
+ * normalises THIS vector instead of forming it again (:134-142 compute the same vector the same way): the call applies ONE PRODUCT
+ * FEWER PER RESTART than the reference's loop counts, and three passes fewer.
+ * info = +n_iter when converged, -n_iter otherwise (:234-238); n_iter counts the inner steps plus one per cycle.  res (may be NULL)
+ * receives at most res_cap entries of the residual history, nres its full length, at most 1 + (maxiter + 1)(kdim + 1); n_inner and
+ * n_outer as in gmres_dp_metadata (IterativeSolvers.fypp:153-170).  nres, n_inner and n_outer may be NULL.
+ * LK_ERR_INVALID, with nothing written: a null A, V or info; kdim out of range; the workspace too narrow; x or b one of the columns of
+ * V the call writes ([0, kdim], [0, kdim + 1] with M); x and b the same column; operator, preconditioner and vectors of different
+ * shape, kind or context; a ROW-SHARDED context (nranks > 1).  LK_ERR_NAN: ||b|| or a residual norm is not finite. */
+int lk_gmres(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t V, double rtol, double atol,
+             int kdim, int maxiter, double *res, int64_t res_cap, int64_t *nres, int *n_inner, int *n_outer, int *info);
 
 #ifdef __cplusplus
 }

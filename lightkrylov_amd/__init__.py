@@ -15,12 +15,12 @@ from .context import Context, default_context, row_partition  # noqa: F401
 from .vectors import (Gram, abstract_vector, axpby_basis, copy, dense_vector_gpu, innerprod,  # noqa: F401
                       krylov_basis_gpu, linear_combination, rand_basis, verify_vector_axioms, zero_basis)
 from .linops import (Id, abstract_linop, adjoint_linop, axpby_linop, scaled_linop, csr_linop_gpu, dense_linop_gpu, diag_linop_gpu, exptA_linop,
-                     ginzburg_landau_linop_gpu, grid_partition, laplacian2d_linop_gpu)  # noqa: F401
+                     ginzburg_landau_linop_gpu, grid_partition, laplacian2d_linop_gpu, compose_linop_gpu, residual)  # noqa: F401
 from .krylov import (arnoldi, bidiagonalization, double_gram_schmidt_step, invperm, is_orthonormal, krylov_schur, lanczos,  # noqa: F401
                      orthogonalize_against_basis, permcols, qr)
 from .expm import expm, kexpm, krylov_exptA, norm2  # noqa: F401
 from .solvers import (apply_givens_rotation, cg, cg_dp_metadata, cg_dp_opts, eig, eighs, eigs, gmres, gmres_dp_metadata,  # noqa: F401
-                      gmres_dp_opts, svds)
+                      gmres_dp_opts, linop_precond_gpu, svds)
 
 from .outputs import save_eigenspectrum, write_results  # noqa: F401
 

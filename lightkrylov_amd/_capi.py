@@ -107,6 +107,10 @@ SIGNATURES = {
     "lk_norm2_dense": (_int, [_int, _int, _int, _dp, _i64, _dp]),
     "lk_qr_pivot": (_int, [_p, _int, _int, _dp, _i64, _ip, C.c_double, _ip]),
     "lk_kexpm_block": (_int, [_p, _int, _p, _int, _p, _int, _int, _p, C.c_double, C.c_double, _int, _ip, _dp]),
+    "lk_linop_compose_create": (_int, [_p, _int, _p, _int, _pp]),
+    "lk_linop_residual": (_int, [_p, _int, _p, _int, _p, _int, _p, _int, _dp]),
+    "lk_gmres": (_int, [_p, _int, _p, _p, _int, _p, _int, _p, C.c_double, C.c_double, _int, _int, _dp, _i64, C.POINTER(_i64), _ip, _ip,
+                        _ip]),
 }
 
 

@@ -3937,4 +3937,283 @@ static int kexpm_block_impl(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_
     return LK_OK;
 }
 
+// ---- residual, and restarted GMRES as one call ---------------------------------------------------------------------------------------
+// r <- b - r and ||r||^2 (2 doubles, imaginary part 0) at out_dev: k_axpby's residual branch + finish_partials + the all-reduce, as dot_device.
+// With A the product op(A) x is enqueued into r first; without, r is taken as it stands.  Arguments validated by the callers.
+static int residual_device(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_basis_t Bb, int jb, lk_basis_t Br, int jr, double *out_dev) {
+    lk_context_t c = Br->ctx;
+    if (A) LKCHK(lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, Bx, jx, Br, jr));
+    Br->touch(jr);
+    const int64_t nv = Br->n * Br->ed() / 2 + 1;
+    int g = blas1_grid(c, nv);
+    if (g > MAX_GRID) g = MAX_GRID;
+    {
+        ProfScope ps(c, "blas1", (double)Br->n * Br->ed() * 24.0);
+        const auto kern = Br->dtype == LK_C128 ? k_axpby<true> : k_axpby<false>;     // its residual branch: the scalars are not read
+        hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, c->stream, 0.0, 0.0, (const double *)Bb->col(jb), 0.0, 0.0, Br->col(jr), Br->n, blas1_nt(Br),
+                           (const double *)nullptr, (double *)c->partial, (int64_t)MAX_GRID);
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(finish_partials, dim3(1), dim3(256), 0, c->stream, c->partial, (int64_t)MAX_GRID, g, 2, out_dev);
+    HIPCHK(hipGetLastError());
+    return allreduce(c, out_dev, 2);
+}
+
+int lk_linop_residual(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_basis_t Bb, int jb, lk_basis_t Br, int jr, double *nrm) {
+    if (!A) return fail(LK_ERR_INVALID, "lk_linop_residual: null operator");
+    LKCHK(check_vec(Bx, jx, "lk_linop_residual(x)"));
+    LKCHK(check_vec(Bb, jb, "lk_linop_residual(b)"));
+    LKCHK(check_vec(Br, jr, "lk_linop_residual(r)"));
+    LKCHK(check_pair(Bx, Br, "lk_linop_residual(x, r)"));
+    LKCHK(check_pair(Bb, Br, "lk_linop_residual(b, r)"));
+    lk_context_t c = Br->ctx;
+    if (A->ctx != c || A->dtype != Br->dtype || A->n != Br->n) return fail(LK_ERR_INVALID, "lk_linop_residual: operator/vector mismatch");
+    if (Br->col(jr) == Bx->col(jx) || Br->col(jr) == Bb->col(jb)) return fail(LK_ERR_INVALID, "lk_linop_residual: r is the same column as x or b");
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    LKCHK(residual_device(A, trans, Bx, jx, Bb, jb, Br, jr, c->red));
+    if (!nrm) return LK_OK;                                      // the sum stays on the device, no synchronisation
+    LKCHK(fetch(c, 0, 1));
+    *nrm = std::sqrt(std::fabs(c->red_host[0]));
+    return LK_OK;
+}
+
+extern "C++" {   // overloads and a template: no C linkage
+namespace {
+// apply_givens_rotation (submodule_utility_functions.fypp:173-204) on column k of H (h: k + 1 entries), and gmres.fypp:180 on e
+void gmres_rotate(double *h, double *c, double *s, double *e, int k) {
+    for (int j = 0; j < k - 1; ++j) {                            // the rotations of the columns before
+        const double t = h[j + 1];
+        h[j + 1] = c[j] * t - s[j] * h[j];
+        h[j] = s[j] * t + c[j] * h[j];
+    }
+    const double f = h[k - 1], g = h[k];
+    double cc, ss, r;
+    if (g == 0.0) { cc = 1.0; ss = 0.0; r = f; }
+    else if (f == 0.0) { cc = 0.0; ss = std::copysign(1.0, g); r = std::fabs(g); }
+    else { const double d = std::hypot(f, g); cc = std::fabs(f) / d; r = std::copysign(d, f); ss = g / r; }
+    c[k - 1] = cc; s[k - 1] = ss;
+    h[k - 1] = r; h[k] = 0.0;
+    e[k] = -ss * e[k - 1];
+    e[k - 1] = cc * e[k - 1];
+}
+void gmres_rotate(std::complex<double> *h, std::complex<double> *c, std::complex<double> *s, std::complex<double> *e, int k) {
+    for (int i = 0; i < k - 1; ++i) {
+        const std::complex<double> t = c[i] * h[i] + s[i] * h[i + 1];
+        h[i + 1] = -s[i] * h[i] + c[i] * h[i + 1];
+        h[i] = t;
+    }
+    const double nrm = std::sqrt(std::norm(h[k - 1]) + std::norm(h[k]));   // givens_rotation: x / norm(x, 2)
+    c[k - 1] = h[k - 1] / nrm; s[k - 1] = h[k] / nrm;
+    h[k - 1] = c[k - 1] * h[k - 1] + s[k - 1] * h[k];
+    h[k] = 0.0;
+    e[k] = -s[k - 1] * e[k - 1];
+    e[k - 1] = c[k - 1] * e[k - 1];
+}
+// y = H(:k, :k)^-1 e(:k), H upper triangular (trtrs, gmres.fypp:199-200); 0, or i + 1 for a zero pivot in row i
+template <class T>
+int gmres_backsolve(const T *H, int64_t ldh, const T *e, int k, T *y) {
+    for (int i = 0; i < k; ++i)
+        if (H[(size_t)i * ldh + i] == T(0.0)) return i + 1;
+    for (int i = k - 1; i >= 0; --i) {
+        T s = e[i];
+        for (int j = i + 1; j < k; ++j) s -= H[(size_t)j * ldh + i] * y[j];
+        y[i] = s / H[(size_t)i * ldh + i];
+    }
+    return 0;
+}
+
+// what the progress function of lk_gmres keeps between the deliveries of a cycle's Arnoldi steps
+struct GmresState {
+    int ED = 1;
+    double *H = nullptr;              // (ldh x kdim), zeroed before every cycle; rotated in place
+    int64_t ldh = 0;
+    double tol = 0.0;
+    const double *s_host = nullptr;   // pinned: ||r0||^2 of the first cycle, on the host before the first delivery
+    bool beta_pending = false;        // e(1) and the first entry of the history are still to be taken from s_host
+    std::vector<double> e, c, s;      // gmres.fypp:112-117, ED doubles per entry
+    std::vector<double> res;          // the residual history
+    int last = 0;                     // last step of this cycle that has been rotated
+    double hsub = 0.0;                // H(last + 1, last) as the step delivered it
+    bool converged = false;
+    int n_iter = 0, n_inner = 0;
+    int rc = LK_OK;
+    // gmres.fypp:178-195 for step k; true when |e(k+1)| < tol
+    bool step(int k) {
+        double r;
+        hsub = H[((size_t)(k - 1) * ldh + k) * ED];
+        if (ED == 2) {
+            typedef std::complex<double> cplx;
+            gmres_rotate(reinterpret_cast<cplx *>(H) + (size_t)(k - 1) * ldh, reinterpret_cast<cplx *>(c.data()), reinterpret_cast<cplx *>(s.data()),
+                         reinterpret_cast<cplx *>(e.data()), k);
+            r = std::hypot(e[2 * (size_t)k], e[2 * (size_t)k + 1]);
+        } else {
+            gmres_rotate(H + (size_t)(k - 1) * ldh, c.data(), s.data(), e.data(), k);
+            r = std::fabs(e[k]);
+        }
+        n_iter += 1; n_inner += 1;
+        res.push_back(r);
+        last = k;
+        if (r != r) { rc = fail(LK_ERR_NAN, "lk_gmres: the residual norm is not finite"); return true; }
+        if (r < tol) converged = true;
+        return converged;
+    }
+};
+
+int gmres_progress(void *user, int kfirst, int klast) {
+    GmresState &st = *static_cast<GmresState *>(user);
+    if (st.beta_pending) {
+        const double beta = std::sqrt(std::fabs(st.s_host[0]));
+        st.beta_pending = false;
+        if (!std::isfinite(beta)) { st.rc = fail(LK_ERR_NAN, "lk_gmres: the residual norm is not finite"); return 1; }
+        st.e[0] = beta;
+        st.res.push_back(beta);
+    }
+    for (int k = kfirst; k <= klast; ++k)
+        if (st.step(k)) return 1;
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+static int gmres_impl(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t V, double bnorm,
+                      double xnorm, double rtol, double atol, int kdim, int maxiter, double *res, int64_t res_cap, int64_t *nres, int *n_inner,
+                      int *n_outer, int *info) {
+    lk_context_t c = V->ctx;
+    const int ED = V->ed();
+    const int64_t ldh = kdim + 1;
+    lk_basis_s Xv = basis_view(V, 0, kdim + 1);                  // arnoldi sizes its factorisation by the basis it is given  arnoldi.fypp:26
+    V->touch(0, kdim + 1 + (M ? 1 : 0));
+    // the operator of the Arnoldi batch: op(A), or op(A) M sequenced through the workspace column behind the basis
+    ComposeOp AM(A, trans, M ? M : A, 0);
+    if (M) AM.tmp.wrap(V->col(kdim + 1));
+    lk_linop_t op = M ? static_cast<lk_linop_t>(&AM) : A;
+    const int op_trans = M ? LK_OP_N : (trans ? LK_OP_H : LK_OP_N);
+    std::vector<double> H((size_t)ldh * kdim * ED), y((size_t)kdim * ED), hcol((size_t)kdim * ED);
+    std::vector<int> segs(kdim);
+    for (int k = 0; k < kdim; ++k) segs[k] = k + 1;
+    GmresState st;
+    st.ED = ED; st.H = H.data(); st.ldh = ldh; st.s_host = c->expm_host;
+    st.tol = atol + rtol * bnorm;                                // :106
+    st.e.resize((size_t)(kdim + 1) * ED); st.c.resize((size_t)kdim * ED); st.s.resize((size_t)kdim * ED);
+    const double tol = st.tol, one[2] = {1.0, 0.0};
+    int outer = 0;
+    bool have_r0 = false;
+    double beta = 0.0;
+    while (!st.converged && outer <= maxiter) {                  // :131
+        std::fill(H.begin(), H.end(), 0.0);
+        std::fill(st.e.begin(), st.e.end(), 0.0);
+        std::fill(st.c.begin(), st.c.end(), 0.0);
+        std::fill(st.s.begin(), st.s.end(), 0.0);
+        if (!have_r0) {
+            // V(1) = b - op(A) x, the product skipped for x = 0 (:134-142); beta^2 stays on the device, the host gets its copy with
+            // the first delivery of the batch
+            if (xnorm != 0.0) {
+                LKCHK(residual_device(A, trans, Bx, jx, Bb, jb, V, 0, c->red));
+            } else {
+                LKCHK(lk_vec_zero(V, 0));
+                LKCHK(residual_device(nullptr, 0, Bx, jx, Bb, jb, V, 0, c->red));
+            }
+            HIPCHK(hipMemcpyAsync(c->expm_host, c->red, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            st.beta_pending = true;
+        } else {
+            st.e[0] = beta;     // V(1) is the residual the last cycle ended with (:205-214), the same vector :134-142 would form again
+        }
+        // V(1) / beta in place, beta read on the device (:143); a zero residual is left as it is and ends the cycle at its first step
+        LKCHK(scal_launch(V, 0, 1.0, 0.0, c->red, std::numeric_limits<double>::min()));
+        st.last = 0;
+        int ainfo = 0;
+        LKCHK(arnoldi_impl(op, &Xv, H.data(), ldh, 1, kdim, tol, op_trans, &ainfo, segs.data(), kdim, gmres_progress, &st));   // :155-195
+        LKCHK(st.rc);
+        if (st.last < 1) return fail(LK_ERR_INVALID, "internal: lk_gmres saw no Arnoldi step");
+        // the batch ended on H(k+1, k) <= tol with the residual still above it: the reference goes on with the unscaled vector (:171-172).
+        // arnoldi has normalised the vector of the step it stopped at, as its qr does down to atol_dp (qr.fypp:164): undone here, to rounding
+        if (!st.converged && ainfo == st.last && st.last < kdim && st.hsub >= ATOL_DP) {
+            const double back[2] = {st.hsub, 0.0};
+            LKCHK(lk_vec_scal(&Xv, st.last, back));
+        }
+        for (int k = st.last + 1; !st.converged && k <= kdim; ++k) {
+            LKCHK(lk_linop_apply(op, op_trans, &Xv, k - 1, &Xv, k));
+            double norms[3];
+            int dinfo = 0;
+            LKCHK(lk_dgs(&Xv, k, &Xv, k, hcol.data(), norms, 0, &dinfo));                       // :167-168
+            double *Hk = H.data() + (size_t)(k - 1) * ldh * ED;
+            memcpy(Hk, hcol.data(), (size_t)k * ED * sizeof(double));
+            set_real(Hk + (size_t)k * ED, ED, norms[2]);
+            if (std::fabs(norms[2]) > tol) {
+                const double inv[2] = {1.0 / norms[2], 0.0};
+                LKCHK(lk_vec_scal(&Xv, k, inv));                                                // :172
+            }
+            st.step(k);
+            LKCHK(st.rc);
+        }
+        const int k = st.last < kdim ? st.last : kdim;
+        // y = H(:k, :k)^-1 e(:k) on the host, dx = V(:, :k) y into the column behind the basis vectors the update reads (:199-201)
+        const int tinfo = ED == 2 ? gmres_backsolve(reinterpret_cast<const std::complex<double> *>(H.data()), ldh,
+                                                    reinterpret_cast<const std::complex<double> *>(st.e.data()), k,
+                                                    reinterpret_cast<std::complex<double> *>(y.data()))
+                                  : gmres_backsolve(H.data(), ldh, st.e.data(), k, y.data());
+        if (tinfo != 0) return fail(LK_ERR_INVALID, "TRTRS failed, info=%d", tinfo);
+        LKCHK(lk_lincomb(&Xv, k, y.data(), 1, V, kdim));
+        int jdx = kdim;
+        if (M) {                                                                                // x += M dx (:201-202); V(1) is free here
+            LKCHK(lk_linop_apply(M, LK_OP_N, V, kdim, V, 0));
+            jdx = 0;
+        }
+        LKCHK(lk_vec_axpby(one, V, jdx, one, Bx, jx));
+        // V(1) = b - op(A) x and its norm (:205-214): the next cycle starts from this vector
+        LKCHK(residual_device(A, trans, Bx, jx, Bb, jb, V, 0, c->red));
+        LKCHK(fetch(c, 0, 1));
+        beta = std::sqrt(std::fabs(c->red_host[0]));
+        st.n_iter += 1;
+        outer += 1;
+        st.res.push_back(beta);
+        if (!std::isfinite(beta)) return fail(LK_ERR_NAN, "lk_gmres: the residual norm is not finite");
+        if (beta < tol) st.converged = true;
+        have_r0 = true;
+    }
+    if (res)
+        for (int64_t i = 0; i < res_cap && i < (int64_t)st.res.size(); ++i) res[i] = st.res[(size_t)i];
+    if (nres) *nres = (int64_t)st.res.size();
+    if (n_inner) *n_inner = st.n_inner;
+    if (n_outer) *n_outer = outer;
+    *info = st.converged ? st.n_iter : -st.n_iter;               // :234-238
+    return LK_OK;
+}
+
+int lk_gmres(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t V, double rtol, double atol,
+             int kdim, int maxiter, double *res, int64_t res_cap, int64_t *nres, int *n_inner, int *n_outer, int *info) {
+    if (!A || !V || !info) return fail(LK_ERR_INVALID, "lk_gmres: null argument");
+    LKCHK(check_vec(Bb, jb, "lk_gmres(b)"));
+    LKCHK(check_vec(Bx, jx, "lk_gmres(x)"));
+    LKCHK(check_pair(Bb, V, "lk_gmres(b, V)"));
+    LKCHK(check_pair(Bx, V, "lk_gmres(x, V)"));
+    lk_context_t c = V->ctx;
+    if (A->ctx != c || A->dtype != V->dtype || A->n != V->n) return fail(LK_ERR_INVALID, "lk_gmres: operator/vector mismatch");
+    if (M && (M->ctx != c || M->dtype != V->dtype || M->n != V->n)) return fail(LK_ERR_INVALID, "lk_gmres: preconditioner/vector mismatch");
+    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_gmres: row-sharded contexts (nranks = %d) are not supported", c->nranks);
+    const int ncw = kdim + 1 + (M ? 1 : 0);                      // columns of V the call writes
+    if (kdim < 2 || kdim > KMAX_WIDE) return fail(LK_ERR_INVALID, "lk_gmres: kdim = %d outside [2, %d]", kdim, KMAX_WIDE);
+    if (V->ncols < ncw)
+        return fail(LK_ERR_INVALID, "lk_gmres: the workspace has %d columns, kdim = %d needs %d%s", V->ncols, kdim, ncw, M ? " with a preconditioner" : "");
+    if (res && res_cap < 0) return fail(LK_ERR_INVALID, "lk_gmres: res_cap = %lld", (long long)res_cap);
+    const double *b = Bb->col(jb), *x = Bx->col(jx);
+    if (x == b) return fail(LK_ERR_INVALID, "lk_gmres: x and b are the same column");
+    if (overlaps(x, V, 0, ncw)) return fail(LK_ERR_INVALID, "lk_gmres: x is one of the workspace columns the call writes");
+    if (overlaps(b, V, 0, ncw)) return fail(LK_ERR_INVALID, "lk_gmres: b is one of the workspace columns the call writes");
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    // the one synchronisation outside the cycles: ||b|| for the tolerance (:106) and ||x|| for the test at :134
+    LKCHK(dot_device(Bb, jb, Bb, jb, c->red));
+    LKCHK(dot_device(Bx, jx, Bx, jx, c->red + RED_SECTION));
+    LKCHK(fetch(c, 0, 2));
+    const double bnorm = std::sqrt(std::fabs(c->red_host[0])), xnorm = std::sqrt(std::fabs(c->red_host[RED_SECTION]));
+    if (!std::isfinite(bnorm)) return fail(LK_ERR_NAN, "lk_gmres: |b| is not finite");
+    try {
+        return gmres_impl(A, trans, M, Bb, jb, Bx, jx, V, bnorm, xnorm, rtol, atol, kdim, maxiter, res, res_cap, nres, n_inner, n_outer, info);
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_gmres: no host memory for the projected problem of %d columns", kdim);
+    }
+}
+
 }  // extern "C"

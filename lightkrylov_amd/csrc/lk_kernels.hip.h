@@ -3299,10 +3299,69 @@ __global__ __launch_bounds__(256) void k_scal(double *__restrict__ x, int64_t n,
 // fused normalise does, but OUT OF PLACE: y = x / ||x|| with ||x||^2 left there by k_dot + finish_partials is one read and one write
 // with no host round trip (the reference's `zero_basis; X(1)%add(b); X(1)%scal(1 / beta)`, ExpmLib.fypp:186-187, is two of each behind
 // a norm on the host).  A norm of zero gives alpha = 0: y = 0, on which the first Arnoldi step breaks down and stops the batch.
+// partial != NULL (block-uniform; lk_linop_residual, the residual of gmres.fypp:134-142 / CG.fypp:108-109): y holds op(A) x on entry and
+// becomes the residual x - y IN PLACE, x being the right-hand side, and this block's share of its squared norm is formed in the same
+// pass: partial[b] = sum |y_i|^2 over the block's rows, partial[pstride + b] = 0 (the imaginary slot of k_dot's layout, so that
+// finish_partials and the all-reduce behind it are dot_device's).  One read-write stream and one read stream, one 16-byte access per
+// stream and lane in flight, as the axpby loops below.  The value is formed as the reference's three calls form it -- sub: (-1) x + 1 y,
+// chsgn: (-1) (.) -- so the vector is theirs bit for bit, signed zeros included; ar, ai, br, bi are not read.  The branch stands in
+// front of the axpby loops, which keep their code.
 template <bool CPLX>
 __global__ __launch_bounds__(256) void k_axpby(double ar, double ai, const double *__restrict__ x, double br,
                                                double bi, double *__restrict__ y, int64_t n, int nt,
-                                               const double *__restrict__ inv_sqrt_of) {
+                                               const double *__restrict__ inv_sqrt_of, double *__restrict__ partial = nullptr,
+                                               int64_t pstride = 0) {
+    if (partial) {
+        constexpr int ED = K<CPLX>::ELEM_DOUBLES;
+        const int64_t nd = n * ED, nv = nd / 2;
+        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+        const v2d *bv = reinterpret_cast<const v2d *>(x);
+        v2d *rv = reinterpret_cast<v2d *>(y);
+        v2d acc = v2d{0.0, 0.0};
+        auto res = [&](v2d bb, v2d rr) {
+            if constexpr (CPLX) {
+                v2d t = cmul(v2d{-1.0, 0.0}, bb);
+                t += cmul(v2d{1.0, 0.0}, rr);
+                return cmul(v2d{-1.0, 0.0}, t);
+            } else {
+                v2d t = bb * -1.0;
+                t += rr * 1.0;
+                return t * -1.0;
+            }
+        };
+        if (nt) {
+            for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+                const v2d bb = __builtin_nontemporal_load(bv + i), rr = __builtin_nontemporal_load(rv + i);
+                const v2d t = res(bb, rr);
+                __builtin_nontemporal_store(t, rv + i);
+                acc += t * t;
+            }
+        } else {
+            for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+                const v2d bb = bv[i], rr = rv[i];
+                const v2d t = res(bb, rr);
+                rv[i] = t;
+                acc += t * t;
+            }
+        }
+        if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            double t = x[nd - 1] * -1.0;
+            t += y[nd - 1] * 1.0;
+            t *= -1.0;
+            y[nd - 1] = t;
+            acc.x += t * t;
+        }
+        __shared__ double red[4];
+        const double s = wave_sum(acc.x + acc.y);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+            partial[pstride + blockIdx.x] = 0.0;
+        }
+        return;
+    }
     if (inv_sqrt_of) {
         const double nr = sqrt(fabs(*inv_sqrt_of));
         ar = nr > 0.0 ? 1.0 / nr : 0.0;

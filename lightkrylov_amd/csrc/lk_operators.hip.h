@@ -279,6 +279,29 @@ struct GlOp final : lk_linop_s {
     }
 };
 
+// ---- product of two operators: y = op_a(A) op_b(B) x -----------------------------------------------------------------------------
+// The factors are NOT owned (they outlive this operator); `apply` only sequences theirs through one scratch vector, so it works
+// wherever both factors do (row-sharded contexts included).  The scratch is the operator's own (lk_linop_compose_create), or a view of
+// caller memory (lk_gmres: a column of its workspace).  No row-local form: rowop() stays the default.
+struct ComposeOp final : lk_linop_s {
+    lk_linop_t A, B;
+    int ta, tb;
+    DevBuf<double> tmp;
+    ComposeOp(lk_linop_t a, int transA, lk_linop_t b, int transB) : lk_linop_s(a->ctx, a->dtype, a->n), A(a), B(b), ta(transA ? 1 : 0), tb(transB ? 1 : 0) {
+        matvec_bytes = a->matvec_bytes + b->matvec_bytes + 2.0 * n * ed() * 8.0;   // the factors' + scratch written, scratch read
+    }
+    int apply(int trans, const double *x, double *y, ProfScope &ps) override {
+        if (trans == LK_OP_N) {
+            LKCHK(B->apply(tb ? LK_OP_H : LK_OP_N, x, tmp, ps));
+            HIPCHK(hipGetLastError());
+            return A->apply(ta ? LK_OP_H : LK_OP_N, tmp, y, ps);
+        }
+        LKCHK(A->apply(ta ? LK_OP_N : LK_OP_H, x, tmp, ps));             // (op_a(A) op_b(B))^H = op_b(B)^H op_a(A)^H
+        HIPCHK(hipGetLastError());
+        return B->apply(tb ? LK_OP_N : LK_OP_H, tmp, y, ps);
+    }
+};
+
 }  // namespace
 }  // extern "C++"
 
@@ -299,6 +322,18 @@ int lk_linop_diag_linspace_create(lk_context_t c, int64_t n_local, int64_t row0,
     if (!c || !op) return fail(LK_ERR_INVALID, "null argument");
     std::unique_ptr<DiagLinOp> o(new DiagLinOp(c, n_local));
     o->row0 = row0; o->d0 = d0; o->dstep = dstep;
+    *op = o.release();
+    return LK_OK;
+}
+
+int lk_linop_compose_create(lk_linop_t A, int transA, lk_linop_t B, int transB, lk_linop_t *op) {
+    if (!A || !B || !op) return fail(LK_ERR_INVALID, "lk_linop_compose_create: null argument");
+    if (A->ctx != B->ctx) return fail(LK_ERR_INVALID, "lk_linop_compose_create: the factors belong to different contexts");
+    if (A->dtype != B->dtype) return fail(LK_ERR_INVALID, "lk_linop_compose_create: the factors are of different kinds");
+    if (A->n != B->n) return fail(LK_ERR_INVALID, "lk_linop_compose_create: the factors have %lld and %lld rows", (long long)A->n, (long long)B->n);
+    DevGuard dev_guard(A->ctx);
+    std::unique_ptr<ComposeOp> o(new ComposeOp(A, transA, B, transB));
+    LKCHK(o->tmp.reserve((o->n + 2) * o->ed()));
     *op = o.release();
     return LK_OK;
 }

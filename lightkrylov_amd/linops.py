@@ -314,6 +314,38 @@ class diag_linop_gpu(_engine_linop):
                                                                 float(dstep), C.byref(self._h)))
 
 
+class compose_linop_gpu(_engine_linop):
+    """The product op_a(A) op_b(B) of two engine operators as an engine operator (lk_linop_compose_create): matvec applies B then A
+    through one scratch vector on the device, rmatvec the adjoint product -- the same kernels and the same bits as the two
+    applications through a temporary, with no Python between them, so arnoldi, kexpm and eigs on the product run fused.  A user's
+    `abstract_linop` that chains two others (AbstractLinops.fypp:58-87).  The factors are kept alive by this object."""
+
+    def __init__(self, A: _engine_linop, B: _engine_linop, transA: bool = False, transB: bool = False):
+        super().__init__(getattr(A, "ctx", None))
+        if not (isinstance(A, _engine_linop) and isinstance(B, _engine_linop)):
+            raise TypeError("compose_linop_gpu needs two engine operators")
+        self.A, self.B, self.transA, self.transB = A, B, bool(transA), bool(transB)
+        self.dtype, self.n = A.dtype, A.n
+        _capi.check(self._lib.lk_linop_compose_create(A._h, 1 if transA else 0, B._h, 1 if transB else 0, C.byref(self._h)))
+
+
+def residual(A: _engine_linop, x: dense_vector_gpu, b: dense_vector_gpu, r: dense_vector_gpu, transpose: bool = False) -> float:
+    """r = b - op(A) x and its norm (gmres.fypp:134-142: matvec, sub, chsgn, norm) as ONE engine call (lk_linop_residual): the product,
+    then one pass that forms r and the sum of its squares.  r may be neither x nor b.  Returns ||r||."""
+    if not isinstance(A, _engine_linop):
+        raise TypeError("residual needs an engine operator")
+    if not all(isinstance(v, dense_vector_gpu) for v in (x, b, r)):
+        raise TypeError("engine operators act on dense_vector_gpu")
+    out = C.c_double()
+    _capi.check(A._lib.lk_linop_residual(A._h, 1 if transpose else 0, x.basis._h, x.col, b.basis._h, b.col, r.basis._h, r.col,
+                                         C.byref(out)))
+    if transpose:
+        A.rmatvec_counter += 1
+    else:
+        A.matvec_counter += 1
+    return float(out.value)
+
+
 class laplacian2d_linop_gpu(_engine_linop):
     """5-point Laplacian on an N x N grid, Dirichlet, scaled by (N+1)^2 (config 3, Poisson).
     Row-sharded runs pass the grid lines this rank owns (`j0`, `nj`, see `grid_partition`): vector rows

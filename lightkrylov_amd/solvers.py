@@ -113,14 +113,62 @@ def _dtype_of(v: abstract_vector):
 
 
 # ------------------------------------------------------------------------------------------
+class linop_precond_gpu:
+    """A fixed right preconditioner given as an engine operator M (e.g. Jacobi: `diag_linop_gpu(1 / diag)`): `apply` overwrites
+    vec with M vec, as `abstract_precond_rdp%apply(vec, k, beta, tol)` does (gmres.fypp:155-165, 201-202) -- the three optional
+    arguments are those the reference hands over; a fixed operator ignores them.  Applied through a temporary, so it serves the
+    step-by-step path as well; `gmres` hands M itself to lk_gmres, where it enters the Arnoldi batch on the device."""
+
+    def __init__(self, M):
+        if not isinstance(M, _engine_linop):
+            raise TypeError("linop_precond_gpu needs an engine operator")
+        self.M = M
+
+    def apply(self, vec, k=None, beta=None, tol=None) -> None:
+        wrk = vec.zeros_like()
+        self.M.apply_matvec(vec, wrk)
+        copy(vec, wrk)
+
+
+def _gmres_engine(A, b, x, rtol, atol, M, kdim, maxiter, transpose, meta) -> int:
+    """gmres as ONE engine call (lk_gmres): restarts, Givens rotations and the triangular solve inside the library."""
+    import ctypes as C
+    from . import _capi
+    V = krylov_basis_gpu(b.basis.n_local, kdim + (2 if M is not None else 1), b.dtype, b.basis.ctx)
+    cap = 1 + (maxiter + 1) * (kdim + 1)
+    res = np.zeros(max(cap, 1))
+    nres, n_inner, n_outer, info = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+    A.reset_counter(transpose, "gmres%init")
+    _capi.check(V._lib.lk_gmres(A._h, 1 if transpose else 0, M._h if M is not None else None, b.basis._h, b.col, x.basis._h, x.col,
+                                V._h, float(rtol), float(atol), kdim, maxiter, res.ctypes.data_as(C.POINTER(C.c_double)), cap,
+                                C.byref(nres), C.byref(n_inner), C.byref(n_outer), C.byref(info)))
+    if meta is not None:
+        meta.n_iter, meta.n_inner, meta.n_outer = abs(info.value), n_inner.value, n_outer.value
+        meta.res = [float(r) for r in res[:nres.value]]
+        meta.converged, meta.info = info.value > 0, info.value
+    A.reset_counter(transpose, "gmres%post")
+    return info.value
+
+
 def gmres(A: abstract_linop, b: abstract_vector, x: abstract_vector, rtol: float = rtol_dp,
           atol: float = atol_dp, preconditioner=None, options: gmres_dp_opts | None = None,
-          transpose: bool = False, meta: gmres_dp_metadata | None = None) -> int:
+          transpose: bool = False, meta: gmres_dp_metadata | None = None, engine: bool | None = None) -> int:
     """Restarted GMRES(kdim).  src/IterativeSolvers/GMRES/gmres.fypp:65-255.
     x is the initial guess and is overwritten by the solution.  Returns info = +n_iter if
-    converged, -n_iter otherwise (:234-238); `meta` (if given) receives the residual history."""
+    converged, -n_iter otherwise (:234-238); `meta` (if given) receives the residual history.
+    `engine` (engine extra): the whole solve as one lk_gmres call.  None takes it exactly when the preconditioner is a
+    `linop_precond_gpu`, A an engine operator, the vectors GPU vectors and the context has one rank; True asks for it on an
+    unpreconditioned solve as well (and raises where it cannot be had); False never.  Unpreconditioned solves without the keyword
+    keep the path below."""
     opts = options or gmres_dp_opts()
     kdim, maxiter = opts.kdim, opts.maxiter
+    able = (isinstance(A, _engine_linop) and isinstance(b, dense_vector_gpu) and isinstance(x, dense_vector_gpu)
+            and (preconditioner is None or isinstance(preconditioner, linop_precond_gpu)) and b.basis.ctx.nranks == 1)
+    if engine and not able:
+        raise TypeError("gmres(engine=True) needs an engine operator, GPU vectors, no preconditioner or a linop_precond_gpu, and one rank")
+    if able and (engine or (engine is None and preconditioner is not None)):
+        return _gmres_engine(A, b, x, rtol, atol, preconditioner.M if preconditioner is not None else None, kdim, maxiter,
+                             transpose, meta)
     dt = _dtype_of(b)
     tol = atol + rtol * b.norm()                                                   # :106
     wrk = b.zeros_like()

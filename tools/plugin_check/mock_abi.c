@@ -287,6 +287,18 @@ int lk_kexpm_block(void *A, int trans, void *Bb, int jb0, void *Bc, int jc0, int
     (void)A; (void)trans; (void)Bb; (void)jb0; (void)Bc; (void)jc0; (void)p; (void)X; (void)tau; (void)tol; (void)nk; (void)info; (void)err_est;
     return fail("lk_kexpm_block is not in the mock");
 }
+int lk_linop_compose_create(void *A, int transA, void *B, int transB, void **op) {
+    (void)A; (void)transA; (void)B; (void)transB; (void)op; return fail("lk_linop_compose_create is not in the mock");
+}
+int lk_linop_residual(void *A, int trans, void *Bx, int jx, void *Bb, int jb, void *Br, int jr, double *nrm) {
+    (void)A; (void)trans; (void)Bx; (void)jx; (void)Bb; (void)jb; (void)Br; (void)jr; (void)nrm; return fail("lk_linop_residual is not in the mock");
+}
+int lk_gmres(void *A, int trans, void *M, void *Bb, int jb, void *Bx, int jx, void *V, double rtol, double atol, int kdim, int maxiter,
+             double *res, int64_t res_cap, int64_t *nres, int *n_inner, int *n_outer, int *info) {
+    (void)A; (void)trans; (void)M; (void)Bb; (void)jb; (void)Bx; (void)jx; (void)V; (void)rtol; (void)atol; (void)kdim; (void)maxiter;
+    (void)res; (void)res_cap; (void)nres; (void)n_inner; (void)n_outer; (void)info;
+    return fail("lk_gmres is not in the mock");
+}
 int lk_comm_get_unique_id(void *id) { memset(id, 0, 128); return LK_OK; }
 int lk_comm_init_rank(mock_ctx *c, int nranks, int rank, const void *id) { (void)c; (void)rank; (void)id; return nranks == 1 ? LK_OK : fail("no collective in the mock"); }
 int lk_comm_info(mock_ctx *c, int *nranks, int *rank) { (void)c; if (nranks) *nranks = 1; if (rank) *rank = 0; return LK_OK; }
