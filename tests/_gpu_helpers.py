@@ -140,6 +140,23 @@ def dgs_longdouble(y, X):
     return h1, h2, y1, y2
 
 
+def step_bound_from(X, y, h1, h2, y1):
+    """(h*, scale) of the a-priori entrywise bound on h = h1 + h2 of one two-pass step of y against X (tests/test_gpu_tile_prefetch.py
+    derives it), from the longdouble h1, h2 and y' of dgs_longdouble(y, X)"""
+    # the scale in double: it multiplies gamma_m, so its own rounding (n u of each entry, added back below) is all that matters.
+    # |X^T X - I| <= |fl(X^T X) - I| + gamma_n |X|^T |X|
+    Xa, ya = np.abs(X), np.abs(y)
+    G = np.abs(X.T @ X - np.eye(X.shape[1])) + gamma(X.shape[0]) * (Xa.T @ Xa)
+    scale = G @ (Xa.T @ ya) + Xa.T @ (ya + Xa @ np.abs(h1).astype(np.float64)) + Xa.T @ np.abs(y1).astype(np.float64) + np.abs(h1 + h2).astype(np.float64)
+    return h1 + h2, scale * (1.0 + 4.0 * X.shape[0] * 2.0 ** -53)
+
+
+def _step_bound(X, y):
+    """(h*, scale) of that bound for one two-pass step of y against X, in longdouble"""
+    h1, h2, y1, _y2 = dgs_longdouble(y, X)
+    return step_bound_from(X, y, h1, h2, y1)
+
+
 def assert_second_pass_matters(h1, h2, y):
     """A condition on the INPUT of a test, not a measurement of the code under test: the reference's own second-pass coefficients reach
     1e-6 |y|, a million times the 1e-12 the results are compared at, so a wrong second pass cannot hide below the bound."""

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import lightkrylov_amd as lk
-from tests._gpu_helpers import (CallerPanel, check_entrywise, device_num_cu, dgs_longdouble, gamma, seeded, skewed_basis)
+from tests._gpu_helpers import (CallerPanel, _step_bound, check_entrywise, device_num_cu, dgs_longdouble, seeded, skewed_basis)
 
 pytestmark = pytest.mark.gpu
 
@@ -95,17 +95,6 @@ def _two_steps(c, A, B, H0, k, transpose, fuse):
     c.sync()
     c.profile_enable(False)
     return H, c.profile_get("dgs_sweep1")[0]
-
-
-def _step_bound(X, y):
-    """(h*, scale) of the module docstring's bound for one two-pass step of y against X, in longdouble"""
-    h1, h2, y1, _y2 = dgs_longdouble(y, X)
-    # the scale in double: it multiplies gamma_m, so its own rounding (n u of each entry, added back below) is all that matters.
-    # |X^T X - I| <= |fl(X^T X) - I| + gamma_n |X|^T |X|
-    Xa, ya = np.abs(X), np.abs(y)
-    G = np.abs(X.T @ X - np.eye(X.shape[1])) + gamma(X.shape[0]) * (Xa.T @ Xa)
-    scale = G @ (Xa.T @ ya) + Xa.T @ (ya + Xa @ np.abs(h1).astype(np.float64)) + Xa.T @ np.abs(y1).astype(np.float64) + np.abs(h1 + h2).astype(np.float64)
-    return h1 + h2, scale * (1.0 + 4.0 * X.shape[0] * 2.0 ** -53)
 
 
 @pytest.mark.parametrize("idx,op", list(enumerate(OPERATORS)), ids=OP_IDS)

@@ -127,9 +127,36 @@ def test_every_reachable_instance_was_dispatched_by_the_gpu_suite(instances):
     assert not unknown, f"coverage record names instances the code object does not hold: {unknown}"
 
 
-def test_coverage_record_states_where_it_was_taken():
+def test_no_instance_declared_unreachable_was_dispatched(instances):
+    """the other half of the manifest's claim: a line that says 'unreachable' while the record shows calls is stale"""
+    calls = read_coverage()
+    stale = sorted((i, calls[i]) for i, why in read_manifest().items() if isinstance(why, str) and calls.get(i, 0) > 0)
+    assert not stale, "tests/kernel_instances.txt declares instances unreachable that profiles/kernel_coverage_gpu_suite.csv shows " \
+                      "dispatched (name the GPU tests that reach them):\n  " + "\n  ".join(f"{i}: {n} calls" for i, n in stale)
+
+
+def _record_commit():
     head = [l for l in open(COVERAGE) if l.startswith("#")]
-    assert any(re.search(r"\bcommit [0-9a-f]{7,}", l) for l in head), "the coverage record must name the commit it was taken at"
+    found = [m.group(1) for l in head for m in [re.search(r"\bcommit ([0-9a-f]{7,})", l)] if m]
+    assert found, "the coverage record must name the commit it was taken at"
+    return found[0]
+
+
+def test_coverage_record_states_where_it_was_taken():
+    _record_commit()
+
+
+def test_coverage_record_was_taken_on_this_history():
+    """the commit the record names is HEAD or one of its ancestors: a record from another branch says nothing about this tree"""
+    sha = _record_commit()
+    if not os.path.exists(os.path.join(ROOT, ".git")):
+        pytest.skip("no .git here (a source archive): the record's commit cannot be placed in the history")
+    head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--verify", "HEAD"], capture_output=True, text=True)
+    if head.returncode != 0:
+        pytest.skip(f"git cannot read this checkout ({head.stderr.strip()}): the record's commit cannot be placed in the history")
+    r = subprocess.run(["git", "-C", ROOT, "merge-base", "--is-ancestor", sha, "HEAD"], capture_output=True, text=True)
+    assert r.returncode == 0, f"the coverage record was taken at commit {sha}, which is not HEAD or an ancestor of it " \
+                              f"(git: {r.stderr.strip() or 'exit ' + str(r.returncode)}); re-take it with tools/kernel_coverage.py"
 
 
 # ---- tuning keys ---------------------------------------------------------------------------------------------------------------
