@@ -349,14 +349,34 @@ struct DevGuard {
     }
 };
 
+// ---- launch helpers: what a launcher still chooses itself is its tile size, its blocks-per-CU multiplier and its cap --------------
+// The block-count rule: one block per unit of `work` (tiles, runs, vectors), at most `cap` (= CUs x the site's multiplier), at most
+// `hard_cap` (MAX_GRID where the partial buffer's stride bounds the grid), at least 1.
+inline int grid_blocks(int64_t work, int64_t cap, int64_t hard_cap = INT64_MAX) {
+    return (int)std::max<int64_t>(std::min({work, cap, hard_cap}), 1);
+}
+// ... with every block on the same number of units: 977 tiles on 768 blocks would leave a second round for 209 of them
+// (panel_dot_cw, n = 10^6 complex: 5.9 TB/s; on 489 blocks of 2 tiles each 6.9)
+inline int grid_even_rounds(int64_t work, int64_t cap) {
+    if (cap > MAX_GRID) cap = MAX_GRID;
+    if (work > cap) {
+        const int64_t rounds = (work + cap - 1) / cap;
+        work = (work + rounds - 1) / rounds;
+    }
+    return (int)std::max<int64_t>(work, 1);
+}
+// One launch inside a profiling scope: the scope's two events ride on the dispatch itself when it asks for that (ps.ext), else a plain
+// launch between the scope's stream markers.  The arguments convert to the kernel's own parameter types (owners read as pointers).
+template <class... KA, class... A>
+inline void launch_profiled(const ProfScope &ps, void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A &&...args) {
+    if (ps.on && ps.ext) hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ps.rec.e0, ps.rec.e1, 0, static_cast<KA>(args)...);
+    else hipLaunchKernelGGL(kern, grid, block, lds, stream, static_cast<KA>(args)...);
+}
+
 // non-temporal accesses for vectors that cannot stay in the 32 MB of L2 anyway (the next kernel re-reads them from HBM)
 inline int blas1_nt(lk_basis_t B) { return (int64_t)B->n * B->ed() * 8 >= (int64_t)32 << 20; }
-inline int blas1_grid(lk_context_t c, int64_t nvec) {
-    int64_t g = (nvec + 255) / 256;
-    int64_t cap = (int64_t)c->num_cu * c->blas1_grid_mult;   // 2 blocks per CU: lk_kernels.hip.h, BLAS-1 header
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
+inline int blas1_grid(lk_context_t c, int64_t nvec, int64_t hard_cap = INT64_MAX) {
+    return grid_blocks((nvec + 255) / 256, (int64_t)c->num_cu * c->blas1_grid_mult, hard_cap);   // 2 blocks per CU: lk_kernels.hip.h, BLAS-1 header
 }
 
 int check_vec(lk_basis_t B, int j, const char *what) {
@@ -384,6 +404,14 @@ int allreduce(lk_context_t c, double *dev, int64_t count) {
     return LK_OK;
 }
 
+// out[s] = the sum over a launch's `nblocks` blocks of partial slot first_slot + s, s < nslots (finish_partials), all-reduced
+int reduce_partials(lk_context_t c, int first_slot, int nslots, int nblocks, double *out) {
+    hipLaunchKernelGGL(finish_partials, dim3((nslots + 3) / 4), dim3(256), 0, c->stream, c->partial + (int64_t)first_slot * MAX_GRID, (int64_t)MAX_GRID,
+                       nblocks, nslots, out);
+    HIPCHK(hipGetLastError());
+    return allreduce(c, out, nslots);
+}
+
 // ---- sweep launcher ---------------------------------------------------------------------
 struct SweepCfg { int WC, kcw, grid; int64_t ntiles; };
 
@@ -401,11 +429,7 @@ SweepCfg sweep_cfg(lk_context_t c, int k, int64_t n, int mult = 0) {
     if (s.kcw < 1) s.kcw = 1;
     const int64_t tile_rows = (int64_t)(NW / WC) * (64 / SC) * K<CPLX>::ROWS;
     int64_t ntiles = (n + tile_rows - 1) / tile_rows;
-    int64_t g = (int64_t)c->num_cu * (mult > 0 ? mult : c->grid_mult);
-    if (g > ntiles) g = ntiles;
-    if (g > MAX_GRID) g = MAX_GRID;
-    if (g < 1) g = 1;
-    s.grid = (int)g;
+    s.grid = grid_blocks(ntiles, (int64_t)c->num_cu * (mult > 0 ? mult : c->grid_mult), MAX_GRID);
     s.ntiles = ntiles;
     return s;
 }
@@ -436,11 +460,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
     if (G > 1) {                             // WC and kcw are the lane-split configuration's; the tiles are G times as tall
         const int64_t tile_rows = (int64_t)(NW / s.WC) * 64 * K<CPLX>::ROWS;
         s.ntiles = (n + tile_rows - 1) / tile_rows;
-        int64_t g = (int64_t)c->num_cu * (c->grid_mult_s3 > 0 ? c->grid_mult_s3 : c->grid_mult);
-        if (g > s.ntiles) g = s.ntiles;
-        if (g > MAX_GRID) g = MAX_GRID;
-        if (g < 1) g = 1;
-        s.grid = (int)g;
+        s.grid = grid_blocks(s.ntiles, (int64_t)c->num_cu * (c->grid_mult_s3 > 0 ? c->grid_mult_s3 : c->grid_mult), MAX_GRID);
     }
     // ALGORITHMIC bytes of the three-sweep schedule: k+1 | k+2 | k+2 columns.  With a fused row operator y is neither
     // read nor (sweeps 1, 2) written: k | k | k+1 columns, plus the column of d an explicit diagonal reads
@@ -460,25 +480,10 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
         auto go = [&](auto uu, int mult) {
             constexpr int UU = decltype(uu)::value;
             const int64_t tile_rows = (int64_t)256 * K<CPLX>::ROWS * UU;
-            int64_t g = (n + tile_rows - 1) / tile_rows;
-            int64_t cap = (int64_t)c->num_cu * mult;
-            if (cap > MAX_GRID) cap = MAX_GRID;
-            if (g > cap) {
-                // every block the same number of tiles: 977 tiles on 768 blocks would leave a second round for 209 of them
-                // (n = 10^6 complex: 5.9 TB/s; on 489 blocks of 2 tiles each 6.9)
-                const int64_t rounds = (g + cap - 1) / cap;
-                g = (g + rounds - 1) / rounds;
-            }
-            if (g < 1) g = 1;
-            nblocks = (int)g;
+            nblocks = grid_even_rounds((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * mult);   // every block the same number of tiles
             const size_t lds = (size_t)4 * (k + 1) * ED * sizeof(double);
             ProfScope ps(c, "dgs_sweep1", bytes, c->prof_ext);
-            if (ps.on && ps.ext)
-                hipExtLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, ps.rec.e0, ps.rec.e1, 0, X, ldx, k,
-                                      y, n, c->partial.get(), (int64_t)MAX_GRID, c->guard(), rop);
-            else
-                hipLaunchKernelGGL((panel_dot_cw<CPLX, UU>), dim3(nblocks), dim3(256), lds, c->stream, X, ldx, k, y, n, c->partial,
-                                   (int64_t)MAX_GRID, c->guard(), rop);
+            launch_profiled(ps, panel_dot_cw<CPLX, UU>, dim3(nblocks), dim3(256), lds, c->stream, X, ldx, k, y, n, c->partial, MAX_GRID, c->guard(), rop);
         };
         // long panels: 8 loads per lane and column on 2 blocks per CU (+1-2 % over 4 on 3 at n = 10^8); short ones keep the
         // smaller tile so every CU still gets several tiles
@@ -493,43 +498,21 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
             // a grid rule of its own (panel_dot_cw's): runs of U block-wide accesses, one block per CU (the run's registers fill the CU's
             // share of the file), and every block the same number of runs
             const int64_t run_rows = (int64_t)NW * 64 * K<CPLX>::ROWS * update_two_u<NW>;
-            int64_t g = (n + run_rows - 1) / run_rows;
-            int64_t cap = (int64_t)c->num_cu;
-            if (cap > MAX_GRID) cap = MAX_GRID;
-            if (g > cap) {
-                const int64_t rounds = (g + cap - 1) / cap;
-                g = (g + rounds - 1) / rounds;
-            }
-            if (g < 1) g = 1;
-            nblocks = (int)g;
-            if (ps.on && ps.ext)
-                hipExtLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, X, ldx,
-                                      k, y, n, hin, hin2, c->partial.get(), (int64_t)MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
-            else
-                hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin, hin2,
-                                   c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
+            nblocks = grid_even_rounds((n + run_rows - 1) / run_rows, c->num_cu);
+            launch_profiled(ps, panel_update<CPLX, KC, NW, MODE == 4>, dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin, hin2, c->partial,
+                            MAX_GRID, c->store_policy, c->guard(), s.WC, s.kcw, rop);
         } else if (MODE == 3) {     // always the streaming kernel: the tile kernel's instances with these flags hold the look-ahead sweep
-            ps.ext = false;
+            ps.ext = false;         // (a plain launch between stream markers: the constructor left e0 to the dispatch, so it is recorded here)
             if (ps.on) (void)hipEventRecord(ps.rec.e0, c->stream);
             const int64_t tile_rows = (int64_t)NW * 64 * K<CPLX>::ROWS;
-            int64_t g = (n + tile_rows - 1) / tile_rows;
-            const int64_t cap = (int64_t)c->num_cu * c->update_grid_mult;
-            if (g > cap) g = cap;
-            if (g > MAX_GRID) g = MAX_GRID;
-            if (g < 1) g = 1;
-            nblocks = (int)g;
-            hipLaunchKernelGGL((panel_update<CPLX, KC, NW, MODE == 4>), dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y,
-                               n, hin, hin2, c->partial, (int64_t)MAX_GRID, c->store_policy, c->guard(), 1, k, RowOp{});
+            nblocks = grid_blocks((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * c->update_grid_mult, MAX_GRID);
+            launch_profiled(ps, panel_update<CPLX, KC, NW, MODE == 4>, dim3(nblocks), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin, hin2, c->partial,
+                            MAX_GRID, c->store_policy, c->guard(), 1, k, RowOp{});
         } else {
             // (MODE 5: panel_sweep<.., true, false, false, 1, 1>, the look-ahead body)
             const int st = (store ? (1 | (c->store_policy << 1) | (c->store_split ? 8 : 0)) : 0) | (c->xcd_map ? 16 : 0);
-            if (ps.on && ps.ext)
-                hipExtLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream,
-                                      ps.rec.e0, ps.rec.e1, 0, X, ldx, k, y, n, hin, hin2, c->partial.get(), (int64_t)MAX_GRID, s.WC, s.kcw, st,
-                                      c->guard(), rop);
-            else
-                hipLaunchKernelGGL((panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>), dim3(s.grid), dim3(NW * 64), 0, c->stream, X,
-                                   ldx, k, y, n, hin, hin2, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, st, c->guard(), rop);
+            launch_profiled(ps, panel_sweep<CPLX, KC, NW, UPDATE, DOT, MODE == 4, SC, G>, dim3(s.grid), dim3(NW * 64), 0, c->stream, X, ldx, k, y, n, hin,
+                            hin2, c->partial, MAX_GRID, s.WC, s.kcw, st, c->guard(), rop);
         }
     }
     HIPCHK(hipGetLastError());
@@ -537,10 +520,7 @@ int launch_sweep(lk_context_t c, const double *X, int64_t ldx, int k, double *y,
     // slots: DOT -> 0..k*ED-1 valid; norm at slot k*ED.  Without DOT only the norm slot is defined.
     const int first = DOT || MODE == 5 ? 0 : k * ED;
     const int nslots = (k + 1) * ED - first + (MODE == 5 ? 2 : 0);
-    hipLaunchKernelGGL(finish_partials, dim3((nslots + 3) / 4), dim3(256), 0, c->stream,
-                       c->partial + (int64_t)first * MAX_GRID, (int64_t)MAX_GRID, nblocks, nslots, out + first);
-    HIPCHK(hipGetLastError());
-    return allreduce(c, out + first, nslots);
+    return reduce_partials(c, first, nslots, nblocks, out + first);
 }
 
 template <int MODE>
@@ -632,12 +612,9 @@ int dots_p(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int pn, double 
         if (P == 2) {
             SweepCfg s = cp ? sweep_cfg<true, 8, 16>(c, k, Bx->n) : sweep_cfg<false, 16, 8>(c, k, Bx->n);
             grid = s.grid;
-            if (cp)
-                hipLaunchKernelGGL((panel_dot_p<true, 8, 16, 2>), dim3(s.grid), dim3(1024), 0, c->stream, Bx->col(c0), Bx->ld, k,
-                                   By->col(jy0), By->ld, pn, Bx->n, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, 0, 1);
-            else
-                hipLaunchKernelGGL((panel_dot_p<false, 16, 8, 2>), dim3(s.grid), dim3(512), 0, c->stream, Bx->col(c0), Bx->ld, k,
-                                   By->col(jy0), By->ld, pn, Bx->n, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, 0, 1);
+            const auto kern = cp ? panel_dot_p<true, 8, 16, 2> : panel_dot_p<false, 16, 8, 2>;
+            hipLaunchKernelGGL(kern, dim3(s.grid), dim3(cp ? 1024 : 512), 0, c->stream, Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld, pn, Bx->n, c->partial,
+                               (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, 0, 1);
         } else {
             constexpr int PANEL = 64;                                  // 16 waves x 4 columns
             auto cfg = [&](int kk) { return cp ? sweep_cfg<true, 4, 16>(c, kk, Bx->n) : sweep_cfg<false, 4, 16>(c, kk, Bx->n); };
@@ -648,23 +625,17 @@ int dots_p(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int pn, double 
                 const int g = cfg((k - j0) < PANEL ? (k - j0) : PANEL).grid;
                 if (g < grid) grid = g;
             }
+            const auto kern = cp ? panel_dot_p<true, 4, 16, 4> : panel_dot_p<false, 4, 16, 4>;
             for (int j0 = 0; j0 < k; j0 += PANEL) {
                 const int kk = (k - j0) < PANEL ? (k - j0) : PANEL;
                 const SweepCfg s = cfg(kk);
-                if (cp)
-                    hipLaunchKernelGGL((panel_dot_p<true, 4, 16, 4>), dim3(grid), dim3(1024), 0, c->stream, Bx->col(c0 + j0), Bx->ld, kk,
-                                       By->col(jy0), By->ld, pn, Bx->n, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, j0, j0 == 0);
-                else
-                    hipLaunchKernelGGL((panel_dot_p<false, 4, 16, 4>), dim3(grid), dim3(1024), 0, c->stream, Bx->col(c0 + j0), Bx->ld, kk,
-                                       By->col(jy0), By->ld, pn, Bx->n, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, j0, j0 == 0);
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), 0, c->stream, Bx->col(c0 + j0), Bx->ld, kk, By->col(jy0), By->ld, pn, Bx->n, c->partial,
+                                   (int64_t)MAX_GRID, s.WC, s.kcw, k + 1, j0, j0 == 0);
             }
         }
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_partials, dim3((nslots + 3) / 4), dim3(256), 0, c->stream, c->partial, (int64_t)MAX_GRID, grid,
-                       nslots, out);
-    HIPCHK(hipGetLastError());
-    return allreduce(c, out, nslots);
+    return reduce_partials(c, 0, nslots, grid, out);
 }
 
 // Passes B and C of the fused block DGS (panel_sweep_p) for columns [jy0, jy0 + pn) of Y against X(:, :k):
@@ -682,9 +653,7 @@ int block_sweeps(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int pn, const dou
                            By->col(jy0), By->ld, pn, Bx->n, out1, nullptr, k + 1, c->partial, (int64_t)MAX_GRID, s.WC, s.kcw, 0, c->guard());
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_partials, dim3((nslots + 3) / 4), dim3(256), 0, c->stream, c->partial, (int64_t)MAX_GRID, s.grid, nslots, out2);
-    HIPCHK(hipGetLastError());
-    LKCHK(allreduce(c, out2, nslots));
+    LKCHK(reduce_partials(c, 0, nslots, s.grid, out2));
     {
         ProfScope ps(c, "dgs_block_sweep3", (double)Bx->n * ED * 8.0 * (k + 2 * pn));
         hipLaunchKernelGGL((panel_sweep_p<CPLX, KC, NW, P, false, true>), dim3(s.grid), dim3(NW * 64), 0, c->stream, Bx->col(0), Bx->ld, k,
@@ -725,10 +694,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
     const bool small = c->xhy_small && PJ <= 2;
     const int TR = (small || cp) ? 32 : 64;     // (complex, more than 32 right-hand sides: 32-row tiles too -- sixteen staged chunks beside 2 x 8 accumulators spilled 68 B)
     const int64_t ntiles = (Bx->n * ED + TR - 1) / TR;
-    int64_t g = (int64_t)c->num_cu * (small ? (c->xhy_grid_mult ? c->xhy_grid_mult : (cp ? 2 : 3)) : 1);
-    if (g > ntiles) g = ntiles;
-    if (g < 1) g = 1;
-    const int grid = (int)g, nvb = grid * WR;
+    const int grid = grid_blocks(ntiles, (int64_t)c->num_cu * (small ? (c->xhy_grid_mult ? c->xhy_grid_mult : (cp ? 2 : 3)) : 1)), nvb = grid * WR;
     // the workspace: two result sections | norm partials | `blocks` partial result blocks.  It grows only while `may_grow` (a later pass of the block step finds the
     // coefficients of the earlier ones in it), and then at once to what the fused block pass needs (two partial blocks per CU), so that no pass has to grow it again
     auto ensure = [&](int64_t blocks) -> int {
@@ -747,9 +713,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
         const int resident = KP == 1 ? 4 : (KP == 2 ? 3 : (KP == 3 ? 2 : 1));                     // blocks per CU (three accumulators per tile: registers)
         const int nbuf = KP == 1 ? 8 : (KP == 2 ? 5 : (KP == 3 ? 3 : 5));                         // (narrow tiles: a deeper ring; 84..140 KB at one block per CU)
         const int64_t nt16 = (Bx->n + 15) / 16;
-        int64_t gg = (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs);
-        if (gg > nt16) gg = nt16;
-        if (gg < 1) gg = 1;
+        const int gg = grid_blocks(nt16, (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs));
         LKCHK(ensure(gg));
         double *outg = c->xhy + (int64_t)slot * XHY_SLOT, *npartg = c->xhy + 2 * sect, *partg = npartg + npart_n;
         const size_t ldsg = (size_t)nbuf * KP * 4096;
@@ -757,7 +721,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
             ProfScope ps(c, "xhy_mfma", (double)Bx->n * ED * 8.0 * k);
             auto go = [&](auto kern) -> int {
                 if (ldsg > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-                hipLaunchKernelGGL(kern, dim3((unsigned)gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
+                hipLaunchKernelGGL(kern, dim3(gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
                 return LK_OK;
             };
             if (KP == 1) LKCHK(go(&panel_gram_rs3m<1, 8, 8>));
@@ -769,7 +733,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
             else LKCHK(go(&panel_gram_rs3m4<7, 5, 2>));
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, (int)gg, npartg, (int)gg, k, p, ED, flags, outg);
+        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, gg, npartg, gg, k, p, ED, flags, outg);
         HIPCHK(hipGetLastError());
         if (out_dev) *out_dev = outg;
         return allreduce(c, outg, nslots);
@@ -777,9 +741,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
     // complex Gram matrix beyond 32 columns: upper tiles dealt to the waves, three real products per complex one (panel_gram_mfma3m)
     if (cp && !small && c->gemm_3m && flags == 3) {
         const int64_t nt32 = (Bx->n + 31) / 32;
-        int64_t gg = (int64_t)c->num_cu;
-        if (gg > nt32) gg = nt32;
-        if (gg < 1) gg = 1;
+        const int gg = grid_blocks(nt32, c->num_cu);
         LKCHK(ensure(gg));
         double *out3 = c->xhy + (int64_t)slot * XHY_SLOT, *npart3 = c->xhy + 2 * sect, *part3 = npart3 + npart_n;
         const size_t lds3 = (size_t)KP * 16 * 34 * 2 * sizeof(double);
@@ -787,10 +749,10 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
             ProfScope ps(c, "xhy_mfma", (double)Bx->n * ED * 8.0 * k);
             if (lds3 > 48 * 1024)
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gram_mfma3m), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-            hipLaunchKernelGGL(panel_gram_mfma3m, dim3((unsigned)gg), dim3(512), lds3, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, part3);
+            hipLaunchKernelGGL(panel_gram_mfma3m, dim3(gg), dim3(512), lds3, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, part3);
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part3, (int)gg, npart3, (int)gg, k, p, ED, flags, out3);
+        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part3, gg, npart3, gg, k, p, ED, flags, out3);
         HIPCHK(hipGetLastError());
         if (out_dev) *out_dev = out3;
         return allreduce(c, out3, nslots);
@@ -800,9 +762,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
         const int resident = KP <= 3 ? 4 : (KP == 4 ? 3 : (KP <= 6 ? 2 : 1));                    // blocks per CU (LDS ring; beyond 96 columns the accumulators)
         const int nbuf = KP == 1 ? 8 : (KP == 2 ? 5 : (KP <= 6 ? 3 : 4));                        // (narrow tiles: a deeper ring, for the bytes in flight)
         const int64_t nt32 = (Bx->n + 31) / 32;
-        int64_t gg = (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs);
-        if (gg > nt32) gg = nt32;
-        if (gg < 1) gg = 1;
+        const int gg = grid_blocks(nt32, (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs));
         LKCHK(ensure(gg));
         double *outg = c->xhy + (int64_t)slot * XHY_SLOT, *npartg = c->xhy + 2 * sect, *partg = npartg + npart_n;
         const size_t ldsg = (size_t)nbuf * KP * 4096;
@@ -810,7 +770,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
             ProfScope ps(c, "xhy_mfma", (double)Bx->n * 8.0 * k);
             auto go = [&](auto kern) -> int {
                 if (ldsg > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-                hipLaunchKernelGGL(kern, dim3((unsigned)gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
+                hipLaunchKernelGGL(kern, dim3(gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
                 return LK_OK;
             };
             switch (KP) {                                                                       // <column blocks, ring buffers, waves per SIMD>
@@ -825,7 +785,7 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
             }
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, (int)gg, npartg, (int)gg, k, p, ED, flags, outg);
+        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, gg, npartg, gg, k, p, ED, flags, outg);
         HIPCHK(hipGetLastError());
         if (out_dev) *out_dev = outg;
         return allreduce(c, outg, nslots);
@@ -878,10 +838,7 @@ int upd_dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, c
     const int64_t sect = (int64_t)XHY_MAX * (XHY_MAX + 1) * 2;
     const int64_t npart_n = (int64_t)c->num_cu * 4 * XHY_MAX;
     const int64_t ntiles = (Bx->n * ED + 31) / 32;
-    int64_t g = (int64_t)c->num_cu * (cp ? 1 : 2);           // 78 KB (real) / 113 KB (complex) of LDS at k = 128: two / one blocks of 4 waves per CU
-    if (g > ntiles) g = ntiles;
-    if (g < 1) g = 1;
-    const int grid = (int)g;
+    const int grid = grid_blocks(ntiles, (int64_t)c->num_cu * (cp ? 1 : 2));   // 78 KB (real) / 113 KB (complex) of LDS at k = 128: two / one blocks of 4 waves per CU
     const int64_t need = 2 * sect + npart_n + (int64_t)grid * nslots;
     if (c->xhy.capacity() < need) {
         // the coefficients of pass A live in this buffer: grow it BEFORE pass A ran (lk_dgs_block sizes it up front), never here
@@ -891,9 +848,7 @@ int upd_dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, c
     // real kind, 17..32 right-hand sides: row-owner waves on LDS-DMA tiles (panel_xhy_upd_rs, round 6): one block of two four-wave teams per CU, two partial blocks per block
     if (!cp && p > 16 && p <= 32 && c->upd_rs) {
         const int KP = (k + 15) / 16;
-        int64_t gr = c->num_cu;
-        if (gr > ntiles) gr = ntiles;
-        if (gr < 1) gr = 1;
+        const int64_t gr = grid_blocks(ntiles, c->num_cu);
         if (c->xhy.capacity() < 2 * sect + npart_n + 2 * gr * nslots)
             return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld)", (long long)c->xhy.capacity());
         const size_t ldsr = (size_t)4 * (KP * 4096 + 8192);
@@ -970,14 +925,11 @@ int gemm_launch_valu(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q
         const int groups = (qn + QB - 1) / QB;
         const int QGB = groups <= 1 ? 1 : (groups == 2 ? 2 : 4);
         const int64_t tile_rows = (int64_t)(4 / QGB) * 64 * (cp ? 1 : 2);
-        int64_t g = (Bx->n + tile_rows - 1) / tile_rows;
-        const int64_t cap = (int64_t)c->num_cu * c->gemm_grid_mult;
-        if (g > cap) g = cap;
-        if (g < 1) g = 1;
+        const int g = grid_blocks((Bx->n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * c->gemm_grid_mult);
         const double *Cp = pack + (int64_t)(q0 / QB) * k * QB * ED;
         ProfScope ps(c, "lincomb", (double)Bx->n * ED * 8.0 * (k + qn * (accumulate ? 2 : 1)));
         auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), 0, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0 + q0), By->ld, qn,
+            hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0 + q0), By->ld, qn,
                                Cp, Bx->n, accumulate, QGB, c->gemm_store_policy, c->guard());
         };
         // columns in flight per lane: 16 (real) / 8 (complex) loads of 16 B for the narrow shapes, half that beside 8-16 accumulators
@@ -1017,16 +969,13 @@ int gemm_mfma_one(lk_context_t c, const double *X, int64_t ldx, int kk, double *
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma<CPLX, NG, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     constexpr int tile_rows = 8 * 2 * (CPLX ? 16 : 32);
-    int64_t g = (n + tile_rows - 1) / tile_rows;
-    const int64_t cap = (int64_t)c->num_cu * (NG >= 8 ? 1 : (NG >= 4 && CPLX ? 2 : c->gemm_grid_mult));
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
+    const int g = grid_blocks((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * (NG >= 8 ? 1 : (NG >= 4 && CPLX ? 2 : c->gemm_grid_mult)));
     if constexpr (!CPLX && NG <= 2) {
         if (accumulate && c->gemm_prefetch_y) {          // the accumulating update of the block Gram-Schmidt: Y's tile loaded ahead of the k-loop
             if (lds > 48 * 1024)
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma<CPLX, NG, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             // (the rolling prefetch of X beside the prefetched tile of Y does not fit the register file: batch schedule here)
-            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, true, false>), dim3((unsigned)g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
+            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, true, false>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
                                c->gemm_store_policy, c->guard());
             HIPCHK(hipGetLastError());
             return LK_OK;
@@ -1040,13 +989,13 @@ int gemm_mfma_one(lk_context_t c, const double *X, int64_t ldx, int kk, double *
         // (k = 64, q = 32: 1.38-1.44 ms both) and keep the batch schedule's three blocks per CU; 2 = every variant that has a ring
         // (the real kind's straight-line ring is unrolled for the basis widths 128 and 64: any other width keeps the batch schedule)
         if ((CPLX || kk == 128 || kk == 64) && (c->gemm_roll >= 2 || (c->gemm_roll == 1 && !CPLX && NG == 4))) {
-            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, true>), dim3((unsigned)g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
+            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, true>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
                                c->gemm_store_policy, c->guard());
             rolled = true;
         }
     }
     if (!rolled)
-        hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, false>), dim3((unsigned)g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
+        hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, false>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
                            c->gemm_store_policy, c->guard());
     HIPCHK(hipGetLastError());
     return LK_OK;
@@ -1064,16 +1013,9 @@ int gemm_mfma3m_one(lk_context_t c, const double *X, int64_t ldx, int kk, double
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma3m<NG, NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     constexpr int tile_rows = 8 * NR * 16;
-    int64_t g = (n + tile_rows - 1) / tile_rows;
-    const int64_t cap = (int64_t)c->num_cu * (NG >= 4 ? 2 : (NG >= 2 ? 2 : c->gemm_grid_mult));
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    if (roll)
-        hipLaunchKernelGGL((panel_gemm_mfma3m<NG, NR, true>), dim3((unsigned)g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
-                           c->gemm_store_policy, c->guard());
-    else
-        hipLaunchKernelGGL((panel_gemm_mfma3m<NG, NR>), dim3((unsigned)g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
-                           c->gemm_store_policy, c->guard());
+    const int g = grid_blocks((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * (NG >= 4 ? 2 : (NG >= 2 ? 2 : c->gemm_grid_mult)));
+    const auto kern = roll ? panel_gemm_mfma3m<NG, NR, true> : panel_gemm_mfma3m<NG, NR>;
+    hipLaunchKernelGGL(kern, dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate, c->gemm_store_policy, c->guard());
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -1160,21 +1102,14 @@ int gemm_launch(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q, con
 int dot_device(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out_dev) {
     lk_context_t c = Bx->ctx;
     const int64_t nv = Bx->n * Bx->ed() / 2 + 1;
-    int g = blas1_grid(c, nv);
-    if (g > MAX_GRID) g = MAX_GRID;
+    const int g = blas1_grid(c, nv, MAX_GRID);   // one partial per block: within the partial buffer's stride
     {
         ProfScope ps(c, "blas1", (double)Bx->n * Bx->ed() * 16.0);
-        if (Bx->dtype == LK_C128)
-            hipLaunchKernelGGL(k_dot<true>, dim3(g), dim3(256), 0, c->stream, Bx->col(jx), By->col(jy), Bx->n, c->partial,
-                               (int64_t)MAX_GRID, blas1_nt(Bx));
-        else
-            hipLaunchKernelGGL(k_dot<false>, dim3(g), dim3(256), 0, c->stream, Bx->col(jx), By->col(jy), Bx->n, c->partial,
-                               (int64_t)MAX_GRID, blas1_nt(Bx));
+        const auto kern = Bx->dtype == LK_C128 ? k_dot<true> : k_dot<false>;
+        hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, c->stream, Bx->col(jx), By->col(jy), Bx->n, c->partial, (int64_t)MAX_GRID, blas1_nt(Bx));
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_partials, dim3(1), dim3(256), 0, c->stream, c->partial, (int64_t)MAX_GRID, g, 2, out_dev);
-    HIPCHK(hipGetLastError());
-    return allreduce(c, out_dev, 2);
+    return reduce_partials(c, 0, 2, g, out_dev);
 }
 
 int fetch(lk_context_t c, int section0, int nsections, int stride = RED_SECTION) {
@@ -1192,12 +1127,9 @@ int scal_launch(lk_basis_t B, int j, double ar, double ai, const double *inv_sqr
     lk_context_t c = B->ctx;
     const int64_t nv = B->n * B->ed() / 2 + 1;
     ProfScope ps(c, "blas1", (double)B->n * B->ed() * 16.0);
-    if (B->dtype == LK_C128)
-        hipLaunchKernelGGL(k_scal<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, B->col(j), B->n, ar, ai,
-                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B), la_sums, la_h1);
-    else
-        hipLaunchKernelGGL(k_scal<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, B->col(j), B->n, ar, ai,
-                           inv_sqrt_of, tol, c->guard(), stop_out, tol_break, blas1_nt(B), la_sums, la_h1);
+    const auto kern = B->dtype == LK_C128 ? k_scal<true> : k_scal<false>;
+    hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, B->col(j), B->n, ar, ai, inv_sqrt_of, tol, c->guard(), stop_out, tol_break,
+                       blas1_nt(B), la_sums, la_h1);
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -1263,12 +1195,9 @@ int materialise_queue(lk_context_t c) {
         if (q.zeroed) c->fusion_stats[3] += 1;
         c->lazy_stats[3] += 1;
         ProfScope ps(c, "blas1", (double)q.Bx->n * q.Bx->ed() * 24.0);
-        if (cp)
-            hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], q.coef[1], q.Bx->col(q.j0), b, 0.0,
-                               T, q.Bx->n, blas1_nt(q.Bx), (const double *)nullptr);
-        else
-            hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], 0.0, q.Bx->col(q.j0), b, 0.0, T,
-                               q.Bx->n, blas1_nt(q.Bx), (const double *)nullptr);
+        const auto kern = cp ? k_axpby<true> : k_axpby<false>;
+        hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], cp ? q.coef[1] : 0.0, q.Bx->col(q.j0), b, 0.0, T, q.Bx->n,
+                           blas1_nt(q.Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0);
         HIPCHK(hipGetLastError());
         return LK_OK;
     }
@@ -1548,19 +1477,14 @@ int dgs_resident_launch(lk_basis_t Bx, int k, double *y, double *out, int rs, bo
             if (sh.ntiles <= (int64_t)res_onchip_tiles(KC) * maxg && sh.WC * KC - k < waste) { onchip_kc = KC; waste = sh.WC * KC - k; }
         }
     const Shape sh = shape(onchip_kc ? onchip_kc : 16);
-    int64_t g = sh.ntiles < maxg ? sh.ntiles : maxg;
-    if (g < 1) g = 1;
+    const int g = grid_blocks(sh.ntiles, maxg);
     const int flags = (normalize ? 1 : 0) | (c->resident_rev ? 2 : 0);
     const long long spin = (long long)c->resident_spin_ms * 100000ll;          // wall_clock64 ticks at 100 MHz
     const double bytes = (double)Bx->n * ED * 8.0 * (3.0 * k + 5.0);
     ProfScope ps(c, "dgs_sweep_resident", bytes, c->prof_ext);
     auto go = [&](auto kern) {
-        if (ps.on && ps.ext)
-            hipExtLaunchKernelGGL(kern, dim3((unsigned)g), dim3(NW * 64), 0, c->stream, ps.rec.e0, ps.rec.e1, 0, Bx->col(c0), Bx->ld, k, y, Bx->n, ws,
-                                  out, rs, sh.WC, sh.kcw, flags, tol_scale, tol_break, stop_out, spin, c->guard());
-        else
-            hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(NW * 64), 0, c->stream, Bx->col(c0), Bx->ld, k, y, Bx->n, ws, out, rs, sh.WC, sh.kcw,
-                               flags, tol_scale, tol_break, stop_out, spin, c->guard());
+        launch_profiled(ps, kern, dim3(g), dim3(NW * 64), 0, c->stream, Bx->col(c0), Bx->ld, k, y, Bx->n, ws, out, rs, sh.WC, sh.kcw, flags, tol_scale, tol_break,
+                        stop_out, spin, c->guard());
     };
     switch (onchip_kc) {
     case 16: if (cp) go(dgs_onchip<true, 16, NW>); else go(dgs_onchip<false, 16, NW>); break;
@@ -2169,12 +2093,9 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
     }
     const int64_t nv = Bx->n * Bx->ed() / 2 + 1;
     ProfScope ps(c, "blas1", (double)Bx->n * Bx->ed() * 24.0);
-    if (cp)
-        hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], alpha[1], Bx->col(jx),
-                           beta[0], beta[1], By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr);
-    else
-        hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], 0.0, Bx->col(jx),
-                           beta[0], 0.0, By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr);
+    const auto kern = cp ? k_axpby<true> : k_axpby<false>;
+    hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], cp ? alpha[1] : 0.0, Bx->col(jx), beta[0], cp ? beta[1] : 0.0,
+                       By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0);
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -2392,10 +2313,8 @@ int lk_vec_rand(lk_basis_t B, int j, uint64_t seed, int64_t row0, int ifnorm) {
         LKCHK(lazy_enter_vec(c, &w, true, nullptr, nullptr));
     }
     B->touch(j);
-    if (B->dtype == LK_C128)
-        hipLaunchKernelGGL(k_rand<true>, dim3(blas1_grid(c, B->n)), dim3(256), 0, c->stream, B->col(j), B->n, seed, row0);
-    else
-        hipLaunchKernelGGL(k_rand<false>, dim3(blas1_grid(c, B->n)), dim3(256), 0, c->stream, B->col(j), B->n, seed, row0);
+    const auto kern = B->dtype == LK_C128 ? k_rand<true> : k_rand<false>;
+    hipLaunchKernelGGL(kern, dim3(blas1_grid(c, B->n)), dim3(256), 0, c->stream, B->col(j), B->n, seed, row0);
     HIPCHK(hipGetLastError());
     if (ifnorm) {
         LKCHK(dot_device(B, j, B, j, c->red));
@@ -3786,12 +3705,9 @@ int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int 
     {
         const int64_t nv = X->n * ED / 2 + 1;
         ProfScope ps(c, "blas1", (double)X->n * ED * 16.0);
-        if (ED == 2)
-            hipLaunchKernelGGL(k_axpby<true>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X),
-                               (const double *)c->red);
-        else
-            hipLaunchKernelGGL(k_axpby<false>, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X),
-                               (const double *)c->red);
+        const auto kern = ED == 2 ? k_axpby<true> : k_axpby<false>;
+        hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X), (const double *)c->red,
+                           (double *)nullptr, (int64_t)0);
         HIPCHK(hipGetLastError());
     }
 
@@ -3945,8 +3861,7 @@ static int residual_device(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_ba
     if (A) LKCHK(lk_linop_apply(A, trans ? LK_OP_H : LK_OP_N, Bx, jx, Br, jr));
     Br->touch(jr);
     const int64_t nv = Br->n * Br->ed() / 2 + 1;
-    int g = blas1_grid(c, nv);
-    if (g > MAX_GRID) g = MAX_GRID;
+    const int g = blas1_grid(c, nv, MAX_GRID);
     {
         ProfScope ps(c, "blas1", (double)Br->n * Br->ed() * 24.0);
         const auto kern = Br->dtype == LK_C128 ? k_axpby<true> : k_axpby<false>;     // its residual branch: the scalars are not read
@@ -3954,9 +3869,7 @@ static int residual_device(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_ba
                            (const double *)nullptr, (double *)c->partial, (int64_t)MAX_GRID);
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_partials, dim3(1), dim3(256), 0, c->stream, c->partial, (int64_t)MAX_GRID, g, 2, out_dev);
-    HIPCHK(hipGetLastError());
-    return allreduce(c, out_dev, 2);
+    return reduce_partials(c, 0, 2, g, out_dev);
 }
 
 int lk_linop_residual(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_basis_t Bb, int jb, lk_basis_t Br, int jr, double *nrm) {

@@ -1,6 +1,6 @@
 // lk_operators.hip.h -- the operators of the C ABI: one type per kind behind lk_linop_s, their creators and lk_linop_apply.
 // Part of lk_engine.hip's translation unit (the kernels are compiled once): included inside its extern "C" block, after the helpers
-// used here -- ProfScope, DevGuard, allreduce, blas1_grid, lazy_enter_vec, check_vec, check_pair.
+// used here -- ProfScope, launch_profiled, DevGuard, allreduce, blas1_grid, lazy_enter_vec, check_vec, check_pair.
 #pragma once
 
 extern "C++" {   // the include sits inside the engine's extern "C" block, and a template cannot have C linkage
@@ -26,8 +26,7 @@ namespace {
 // the single kernel (256 threads per block) of an operator with `one_kernel` set: the extended launch when the scope wants its events on the dispatch
 template <class... A, class... B>
 int launch_in_scope(ProfScope &ps, void (*kern)(A...), int grid, const B &...args) {
-    if (ps.on && ps.ext) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ps.c->stream, ps.rec.e0, ps.rec.e1, 0, static_cast<A>(args)...);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ps.c->stream, args...);
+    launch_profiled(ps, kern, dim3(grid), dim3(256), 0, ps.c->stream, args...);
     return LK_OK;
 }
 
