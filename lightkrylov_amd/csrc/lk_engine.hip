@@ -372,6 +372,14 @@ inline void launch_profiled(const ProfScope &ps, void (*kern)(KA...), dim3 grid,
     if (ps.on && ps.ext) hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ps.rec.e0, ps.rec.e1, 0, static_cast<KA>(args)...);
     else hipLaunchKernelGGL(kern, grid, block, lds, stream, static_cast<KA>(args)...);
 }
+// One launch with `lds` bytes of dynamic LDS: more than the default limit of 48 KB needs the opt-in (gfx950: 160 KB per workgroup), asked
+// for the instance that is launched, at every launch.  Arguments typed as in launch_profiled.
+template <class... KA, class... A>
+inline int launch_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A &&...args) {
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, static_cast<KA>(args)...);
+    return LK_OK;
+}
 
 // non-temporal accesses for vectors that cannot stay in the 32 MB of L2 anyway (the next kernel re-reads them from HBM)
 inline int blas1_nt(lk_basis_t B) { return (int64_t)B->n * B->ed() * 8 >= (int64_t)32 << 20; }
@@ -669,129 +677,124 @@ constexpr int XHY_MIN_P = 5;        // fewer right-hand sides: panel_dot_p (<= 4
 constexpr int XHY_MAX = 128;        // columns of X and of Y per launch
 constexpr int XHY_GROUP = 32;       // right-hand sides per pass of the block DGS (beyond ~32 the pass turns MFMA-bound)
 
-// M = X(:, c0 : c0+k)^H Y(:, jy0 : jy0+p), k, p <= XHY_MAX, into result section `sec` (0 / 1) of c->xhy in panel_dot_p's
-// layout [q][k+1][ED] (slot k = ||Y_q||^2), all-reduced.  flags: see the kernel (1 = Y is X, 2 = upper tiles only).
-// `slot`: where in the result area the matrix lands, in units of XHY_SLOT doubles (= one group of XHY_GROUP right-hand sides against
-// XHY_MAX columns): 0 and XHY_SLOTS / 2 are the two classic sections; the block DGS of a basis wider than XHY_MAX columns keeps one
-// slot per column panel of X for H1 (0..3) and one for H2 (4..7).  `may_grow` = false: the workspace already holds coefficients of an
-// earlier pass and must not be re-allocated (the caller sized it with the first pass).
+// The workspace c->xhy of these launchers, for one result matrix of `nslots` = p (k + 1) ED doubles:
+//   two result sections of XHY_MAX (XHY_MAX + 1) 2 doubles, cut into XHY_SLOTS result slots | norm partials | partial result blocks of `nslots` doubles each.
+// A result slot holds one group of XHY_GROUP right-hand sides against XHY_MAX columns: 0 and XHY_SLOTS / 2 are the two classic sections; the block DGS of a
+// basis wider than XHY_MAX columns keeps one slot per column panel of X for H1 (0..3) and one for H2 (4..7).
 constexpr int XHY_SLOTS = 8;
 constexpr int64_t XHY_SLOT = (int64_t)XHY_MAX * (XHY_MAX + 1) * 2 * 2 / XHY_SLOTS;   // = XHY_GROUP * (XHY_MAX + 1) * 2 doubles
 static_assert(XHY_SLOT == (int64_t)XHY_GROUP * (XHY_MAX + 1) * 2, "eight groups of 32 right-hand sides fill the two result sections");
+struct XhyWorkspace {
+    lk_context_t c;
+    int64_t nslots;
+    static constexpr int64_t RESULTS = XHY_SLOTS * XHY_SLOT;                    // the two result sections
+    int64_t npart_n() const { return (int64_t)c->num_cu * 4 * XHY_MAX; }      // norm partials: up to 4 blocks per CU x XHY_MAX right-hand sides
+    double *out(int slot) const { return c->xhy + (int64_t)slot * XHY_SLOT; }
+    double *npart() const { return c->xhy + RESULTS; }
+    double *part() const { return npart() + npart_n(); }
+    int64_t doubles_for(int64_t blocks) const { return RESULTS + npart_n() + blocks * nslots; }
+    bool holds(int64_t blocks) const { return c->xhy.capacity() >= doubles_for(blocks); }
+    // It grows only while `may_grow` (a later pass of the block step finds the coefficients of the earlier ones in it), and then at once to what the
+    // fused block pass needs (two partial blocks per CU), so that no pass has to grow it again.
+    int ensure(int64_t blocks, bool may_grow) const {
+        int64_t need = doubles_for(blocks);
+        // (the fused pass's share counts BEFORE the early return: on a panel of fewer row tiles than CUs this pass needs less than the fused one, and a workspace
+        //  that an earlier, smaller shape had grown could hold this pass and not the next -- k = 64 then 128 with 17 right-hand sides at n = 4099)
+        if (may_grow) need = std::max(need, doubles_for((int64_t)c->num_cu * 2));
+        if (c->xhy.capacity() >= need) return LK_OK;
+        if (!may_grow)
+            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for a later pass of the block Gram-Schmidt (%lld < %lld)", (long long)c->xhy.capacity(), (long long)need);
+        return c->xhy.reserve(need);
+    }
+};
+// The step behind every kernel of this section: result slot `slot` = the sum of the `nblocks` partial blocks, its norms the sum of the `nnorm` norm
+// partials (finish_xhy), all-reduced; *out_dev = where it landed.
+int finish_xhy_step(lk_context_t c, const XhyWorkspace &ws, int nblocks, int nnorm, int k, int p, int ED, int flags, int slot, double **out_dev) {
+    double *out = ws.out(slot);
+    hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((ws.nslots + 15) / 16)), dim3(256), 0, c->stream, ws.part(), nblocks, ws.npart(), nnorm, k, p, ED, flags, out);
+    HIPCHK(hipGetLastError());
+    if (out_dev) *out_dev = out;
+    return allreduce(c, out, ws.nslots);
+}
+
+// The row-split Gram kernels (round 6: the rows of the staged tile dealt to the waves, tiles staged by LDS-DMA into a ring of `nbuf` buffers of KP x 4 KB), by
+// KP = column blocks of 16.  The kernel's template arguments are <column blocks, ring buffers, waves per SIMD>; `resident` = blocks per CU at "gram_rs" = 1.
+using GramRsKernel = void (*)(const double *, int64_t, int, int64_t, double *);
+struct GramRs { GramRsKernel kern; int resident, nbuf; };
+// real kind, 5..128 columns, tiles of 32 rows (panel_gram_rs): the blocks per CU are what the LDS ring leaves room for, beyond 96 columns the accumulators
+const GramRs GRAM_RS_REAL[8] = {
+    {panel_gram_rs<1, 8, 8>, 4, 8},       // (narrow tiles: a deeper ring, for the bytes in flight)
+    {panel_gram_rs<2, 5, 8>, 4, 5},
+    {panel_gram_rs<3, 3, 8>, 4, 3},
+    {panel_gram_rs<4, 3, 6>, 3, 3},
+    {panel_gram_rs<5, 3, 4>, 2, 3},
+    {panel_gram_rs<6, 3, 4>, 2, 3},
+    {panel_gram_rs<7, 4, 2>, 1, 4},
+    {panel_gram_rs<8, 4, 2>, 1, 4},
+};
+// complex kind, 5..112 columns, tiles of 16 rows, three real products per complex one (panel_gram_rs3m / rs3m4): three accumulators per tile, so the
+// registers set the blocks per CU
+const GramRs GRAM_RS_CPLX[7] = {
+    {panel_gram_rs3m<1, 8, 8>, 4, 8},     // (narrow tiles: a deeper ring;
+    {panel_gram_rs3m<2, 5, 6>, 3, 5},
+    {panel_gram_rs3m<3, 3, 4>, 2, 3},
+    {panel_gram_rs3m<4, 5, 2>, 1, 5},     //  84..140 KB at one block per CU)
+    {panel_gram_rs3m<5, 5, 2>, 1, 5},
+    {panel_gram_rs3m4<6, 5, 2>, 1, 5},    // four groups of two waves: a quarter of the tile list each
+    {panel_gram_rs3m4<7, 5, 2>, 1, 5},
+};
+// panel_xhy_mfma's variants [kind][<= 128 | <= 32 right-hand sides][double-buffered]: <kind, right-hand-side tiles, rows per tile, double-buffered>
+// (complex, more than 32 right-hand sides: 32-row tiles too -- sixteen staged chunks beside 2 x 8 accumulators spilled 68 B)
+using XhyKernel = void (*)(const double *, int64_t, int, const double *, int64_t, int, int64_t, int, int, double *, double *);
+const XhyKernel XHY_MFMA[2][2][2] = {
+    {{panel_xhy_mfma<false, 8, 64, false>, panel_xhy_mfma<false, 8, 64, true>}, {panel_xhy_mfma<false, 2, 32, false>, panel_xhy_mfma<false, 2, 32, true>}},
+    {{panel_xhy_mfma<true, 8, 32, false>, panel_xhy_mfma<true, 8, 32, true>}, {panel_xhy_mfma<true, 2, 32, false>, panel_xhy_mfma<true, 2, 32, true>}},
+};
+
+// M = X(:, c0 : c0+k)^H Y(:, jy0 : jy0+p), k, p <= XHY_MAX, into result slot `slot` (0..7) of c->xhy in panel_dot_p's
+// layout [q][k+1][ED] (slot k = ||Y_q||^2), all-reduced.  flags: see the kernel (1 = Y is X, 2 = upper tiles only).
+// `may_grow` = false: the workspace already holds coefficients of an earlier pass and must not be re-allocated (the caller sized it
+// with the first pass).
 int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int flags, int slot, double **out_dev, bool may_grow = true) {
     lk_context_t c = Bx->ctx;
     const bool cp = Bx->dtype == LK_C128;
     const int ED = Bx->ed();
     const int KP = (k + 15) / 16, PJ = (p + 15) / 16;
-    const int NI = KP <= 1 ? 1 : (KP == 2 ? 2 : (KP <= 4 ? 4 : 8));
-    const int WR = 8 / NI;
-    const int64_t nslots = (int64_t)p * (k + 1) * ED;
-    const int64_t sect = (int64_t)XHY_MAX * (XHY_MAX + 1) * 2;                  // doubles per result section
-    const int64_t npart_n = (int64_t)c->num_cu * 4 * XHY_MAX;
+    const XhyWorkspace ws{c, (int64_t)p * (k + 1) * ED};
     // <= 32 right-hand sides: 32-row tiles and a quarter of the accumulators -- 40 KB of LDS and 66-88 VGPRs, so several blocks
     // share a CU and cover each other's barriers and load latency (n = 10^7 real, k = 128, p = 16: 2.54 -> 1.92 ms on 3 blocks
     // per CU, one pass over X at 6.5 TB/s being 1.77; complex 3.73 -> 2.29 ms on 2)
     const bool small = c->xhy_small && PJ <= 2;
-    const int TR = (small || cp) ? 32 : 64;     // (complex, more than 32 right-hand sides: 32-row tiles too -- sixteen staged chunks beside 2 x 8 accumulators spilled 68 B)
-    const int64_t ntiles = (Bx->n * ED + TR - 1) / TR;
-    const int grid = grid_blocks(ntiles, (int64_t)c->num_cu * (small ? (c->xhy_grid_mult ? c->xhy_grid_mult : (cp ? 2 : 3)) : 1)), nvb = grid * WR;
-    // the workspace: two result sections | norm partials | `blocks` partial result blocks.  It grows only while `may_grow` (a later pass of the block step finds the
-    // coefficients of the earlier ones in it), and then at once to what the fused block pass needs (two partial blocks per CU), so that no pass has to grow it again
-    auto ensure = [&](int64_t blocks) -> int {
-        int64_t need = 2 * sect + npart_n + blocks * nslots;
-        // (the fused pass's share counts BEFORE the early return: on a panel of fewer row tiles than CUs this pass needs less than the fused one, and a workspace
-        //  that an earlier, smaller shape had grown could hold this pass and not the next -- k = 64 then 128 with 17 right-hand sides at n = 4099)
-        const int64_t fused = 2 * sect + npart_n + (int64_t)c->num_cu * 2 * nslots;
-        if (may_grow && need < fused) need = fused;
-        if (c->xhy.capacity() >= need) return LK_OK;
-        if (!may_grow)
-            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for a later pass of the block Gram-Schmidt (%lld < %lld)", (long long)c->xhy.capacity(), (long long)need);
-        return c->xhy.reserve(need);
-    };
-    // complex Gram matrix of 5..112 columns: panel_gram_rs's row split and LDS-DMA tiles with three real products per complex one (panel_gram_rs3m / rs3m4, round 6)
-    if (cp && c->gemm_3m && flags == 3 && KP <= 7 && c->gram_rs > 0) {
-        const int resident = KP == 1 ? 4 : (KP == 2 ? 3 : (KP == 3 ? 2 : 1));                     // blocks per CU (three accumulators per tile: registers)
-        const int nbuf = KP == 1 ? 8 : (KP == 2 ? 5 : (KP == 3 ? 3 : 5));                         // (narrow tiles: a deeper ring; 84..140 KB at one block per CU)
-        const int64_t nt16 = (Bx->n + 15) / 16;
-        const int gg = grid_blocks(nt16, (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs));
-        LKCHK(ensure(gg));
-        double *outg = c->xhy + (int64_t)slot * XHY_SLOT, *npartg = c->xhy + 2 * sect, *partg = npartg + npart_n;
-        const size_t ldsg = (size_t)nbuf * KP * 4096;
+    // Gram matrix (Y is X, upper tiles only) on the row-split kernels: real of 5..128 columns, complex of 5..112 on three real products per complex one
+    if (flags == 3 && c->gram_rs > 0 && (cp ? c->gemm_3m && KP <= 7 : k <= 128)) {
+        const GramRs &v = cp ? GRAM_RS_CPLX[KP - 1] : GRAM_RS_REAL[KP - 1];
+        const int rows = cp ? 16 : 32;
+        const int gg = grid_blocks((Bx->n + rows - 1) / rows, (int64_t)c->num_cu * (c->gram_rs == 1 ? v.resident : c->gram_rs));
+        LKCHK(ws.ensure(gg, may_grow));
         {
             ProfScope ps(c, "xhy_mfma", (double)Bx->n * ED * 8.0 * k);
-            auto go = [&](auto kern) -> int {
-                if (ldsg > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-                hipLaunchKernelGGL(kern, dim3(gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
-                return LK_OK;
-            };
-            if (KP == 1) LKCHK(go(&panel_gram_rs3m<1, 8, 8>));
-            else if (KP == 2) LKCHK(go(&panel_gram_rs3m<2, 5, 6>));
-            else if (KP == 3) LKCHK(go(&panel_gram_rs3m<3, 3, 4>));
-            else if (KP == 4) LKCHK(go(&panel_gram_rs3m<4, 5, 2>));
-            else if (KP == 5) LKCHK(go(&panel_gram_rs3m<5, 5, 2>));
-            else if (KP == 6) LKCHK(go(&panel_gram_rs3m4<6, 5, 2>));                              // four groups of two waves: a quarter of the tile list each
-            else LKCHK(go(&panel_gram_rs3m4<7, 5, 2>));
+            LKCHK(launch_lds(v.kern, dim3(gg), dim3(512), (size_t)v.nbuf * KP * 4096, c->stream, Bx->col(c0), Bx->ld, k, Bx->n, ws.part()));
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, gg, npartg, gg, k, p, ED, flags, outg);
-        HIPCHK(hipGetLastError());
-        if (out_dev) *out_dev = outg;
-        return allreduce(c, outg, nslots);
+        return finish_xhy_step(c, ws, gg, gg, k, p, ED, flags, slot, out_dev);
     }
     // complex Gram matrix beyond 32 columns: upper tiles dealt to the waves, three real products per complex one (panel_gram_mfma3m)
     if (cp && !small && c->gemm_3m && flags == 3) {
-        const int64_t nt32 = (Bx->n + 31) / 32;
-        const int gg = grid_blocks(nt32, c->num_cu);
-        LKCHK(ensure(gg));
-        double *out3 = c->xhy + (int64_t)slot * XHY_SLOT, *npart3 = c->xhy + 2 * sect, *part3 = npart3 + npart_n;
-        const size_t lds3 = (size_t)KP * 16 * 34 * 2 * sizeof(double);
+        const int gg = grid_blocks((Bx->n + 31) / 32, c->num_cu);
+        LKCHK(ws.ensure(gg, may_grow));
         {
             ProfScope ps(c, "xhy_mfma", (double)Bx->n * ED * 8.0 * k);
-            if (lds3 > 48 * 1024)
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gram_mfma3m), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-            hipLaunchKernelGGL(panel_gram_mfma3m, dim3(gg), dim3(512), lds3, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, part3);
+            LKCHK(launch_lds(panel_gram_mfma3m, dim3(gg), dim3(512), (size_t)KP * 16 * 34 * 2 * sizeof(double), c->stream, Bx->col(c0), Bx->ld, k, Bx->n, ws.part()));
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part3, gg, npart3, gg, k, p, ED, flags, out3);
-        HIPCHK(hipGetLastError());
-        if (out_dev) *out_dev = out3;
-        return allreduce(c, out3, nslots);
+        return finish_xhy_step(c, ws, gg, gg, k, p, ED, flags, slot, out_dev);
     }
-    // real Gram matrix of 5..128 columns: the rows of the staged tile dealt to the waves, tiles staged by LDS-DMA (panel_gram_rs, round 6)
-    if (!cp && flags == 3 && k <= 128 && c->gram_rs > 0) {
-        const int resident = KP <= 3 ? 4 : (KP == 4 ? 3 : (KP <= 6 ? 2 : 1));                    // blocks per CU (LDS ring; beyond 96 columns the accumulators)
-        const int nbuf = KP == 1 ? 8 : (KP == 2 ? 5 : (KP <= 6 ? 3 : 4));                        // (narrow tiles: a deeper ring, for the bytes in flight)
-        const int64_t nt32 = (Bx->n + 31) / 32;
-        const int gg = grid_blocks(nt32, (int64_t)c->num_cu * (c->gram_rs == 1 ? resident : c->gram_rs));
-        LKCHK(ensure(gg));
-        double *outg = c->xhy + (int64_t)slot * XHY_SLOT, *npartg = c->xhy + 2 * sect, *partg = npartg + npart_n;
-        const size_t ldsg = (size_t)nbuf * KP * 4096;
-        {
-            ProfScope ps(c, "xhy_mfma", (double)Bx->n * 8.0 * k);
-            auto go = [&](auto kern) -> int {
-                if (ldsg > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg));
-                hipLaunchKernelGGL(kern, dim3(gg), dim3(512), ldsg, c->stream, (const double *)Bx->col(c0), Bx->ld, k, Bx->n, partg);
-                return LK_OK;
-            };
-            switch (KP) {                                                                       // <column blocks, ring buffers, waves per SIMD>
-            case 1: LKCHK(go(&panel_gram_rs<1, 8, 8>)); break;
-            case 2: LKCHK(go(&panel_gram_rs<2, 5, 8>)); break;
-            case 3: LKCHK(go(&panel_gram_rs<3, 3, 8>)); break;
-            case 4: LKCHK(go(&panel_gram_rs<4, 3, 6>)); break;
-            case 5: LKCHK(go(&panel_gram_rs<5, 3, 4>)); break;
-            case 6: LKCHK(go(&panel_gram_rs<6, 3, 4>)); break;
-            case 7: LKCHK(go(&panel_gram_rs<7, 4, 2>)); break;
-            default: LKCHK(go(&panel_gram_rs<8, 4, 2>)); break;
-            }
-        }
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, partg, gg, npartg, gg, k, p, ED, flags, outg);
-        HIPCHK(hipGetLastError());
-        if (out_dev) *out_dev = outg;
-        return allreduce(c, outg, nslots);
-    }
-    LKCHK(ensure(nvb));
-    double *out = c->xhy + (int64_t)slot * XHY_SLOT, *npart = c->xhy + 2 * sect, *part = npart + npart_n;
+    const int NI = KP <= 1 ? 1 : (KP == 2 ? 2 : (KP <= 4 ? 4 : 8));
+    const int WR = 8 / NI;
+    const int TR = (small || cp) ? 32 : 64;
+    const int64_t ntiles = (Bx->n * ED + TR - 1) / TR;
+    const int grid = grid_blocks(ntiles, (int64_t)c->num_cu * (small ? (c->xhy_grid_mult ? c->xhy_grid_mult : (cp ? 2 : 3)) : 1)), nvb = grid * WR;
+    LKCHK(ws.ensure(nvb, may_grow));
     // complex kind, <= 32 right-hand sides: three real products per complex one on separate real / imaginary planes ("gemm_3m")
     const bool three = cp && small && c->gemm_3m && !(flags & 1);
     size_t lds = three ? (size_t)(KP + PJ) * 16 * 18 * 2 * sizeof(double)
@@ -802,98 +805,50 @@ int dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, int f
     if (db) lds *= 2;
     {
         ProfScope ps(c, "xhy_mfma", (double)Bx->n * ED * 8.0 * (k + ((flags & 1) ? 0 : p)));
-        auto go = [&](auto kern) -> int {
-            if (lds > 48 * 1024)
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, c->stream, (const double *)Bx->col(c0), Bx->ld, k, (const double *)By->col(jy0), By->ld,
-                               p, Bx->n, flags | (c->xhy_debug << 4), NI, part, npart);
-            return LK_OK;
-        };
-        // variant = (kind, <= 32 | <= 128 right-hand sides, rows per tile, double-buffered)
-        auto pick = [&](auto cplx) -> int {
-            constexpr bool CP = decltype(cplx)::value;
-            if (small) return db ? go(&panel_xhy_mfma<CP, 2, 32, true>) : go(&panel_xhy_mfma<CP, 2, 32, false>);
-            if constexpr (CP) return db ? go(&panel_xhy_mfma<true, 8, 32, true>) : go(&panel_xhy_mfma<true, 8, 32, false>);
-            else return db ? go(&panel_xhy_mfma<false, 8, 64, true>) : go(&panel_xhy_mfma<false, 8, 64, false>);
-        };
-        if (three) LKCHK(go(&panel_xhy_mfma3m));
-        else if (cp) LKCHK(pick(std::true_type{}));
-        else LKCHK(pick(std::false_type{}));
+        LKCHK(launch_lds(three ? panel_xhy_mfma3m : XHY_MFMA[cp][small][db], dim3(grid), dim3(512), lds, c->stream, Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld,
+                         p, Bx->n, flags | (c->xhy_debug << 4), NI, ws.part(), ws.npart()));
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part, nvb, npart, grid, k, p, ED, flags, out);
-    HIPCHK(hipGetLastError());
-    if (out_dev) *out_dev = out;
-    return allreduce(c, out, nslots);
+    return finish_xhy_step(c, ws, nvb, grid, k, p, ED, flags, slot, out_dev);
 }
 
 // Pass B of the block DGS with many right-hand sides, fused (panel_xhy_upd_mfma): Y(:, jy0 : jy0+p) -= X(:, :k) H1, stored, and
-// M2 = X^H Y', ||Y'_q||^2 into result section `sec` of c->xhy (panel_dot_p's layout, all-reduced).  k <= 128, p <= 32.
+// M2 = X^H Y', ||Y'_q||^2 into result slot `slot` (0..7) of c->xhy (panel_dot_p's layout, all-reduced).  k <= 128, p <= 32.
 int upd_dots_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int p, const double *H1dev, int slot, double **out_dev) {
     lk_context_t c = Bx->ctx;
     const bool cp = Bx->dtype == LK_C128;
     const int ED = Bx->ed();
     const int KG = (k + 31) / 32;
-    const int64_t nslots = (int64_t)p * (k + 1) * ED;
-    const int64_t sect = (int64_t)XHY_MAX * (XHY_MAX + 1) * 2;
-    const int64_t npart_n = (int64_t)c->num_cu * 4 * XHY_MAX;
+    const XhyWorkspace ws{c, (int64_t)p * (k + 1) * ED};
     const int64_t ntiles = (Bx->n * ED + 31) / 32;
     const int grid = grid_blocks(ntiles, (int64_t)c->num_cu * (cp ? 1 : 2));   // 78 KB (real) / 113 KB (complex) of LDS at k = 128: two / one blocks of 4 waves per CU
-    const int64_t need = 2 * sect + npart_n + (int64_t)grid * nslots;
-    if (c->xhy.capacity() < need) {
+    if (!ws.holds(grid)) {
         // the coefficients of pass A live in this buffer: grow it BEFORE pass A ran (lk_dgs_block sizes it up front), never here
-        return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld < %lld)", (long long)c->xhy.capacity(), (long long)need);
+        return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld < %lld)", (long long)c->xhy.capacity(), (long long)ws.doubles_for(grid));
     }
-    double *out = c->xhy + (int64_t)slot * XHY_SLOT, *npart = c->xhy + 2 * sect, *part = npart + npart_n;
     // real kind, 17..32 right-hand sides: row-owner waves on LDS-DMA tiles (panel_xhy_upd_rs, round 6): one block of two four-wave teams per CU, two partial blocks per block
     if (!cp && p > 16 && p <= 32 && c->upd_rs) {
+        static const decltype(&panel_xhy_upd_rs<1>) UPD_RS[8] = {panel_xhy_upd_rs<1>, panel_xhy_upd_rs<2>, panel_xhy_upd_rs<3>, panel_xhy_upd_rs<4>,
+                                                                 panel_xhy_upd_rs<5>, panel_xhy_upd_rs<6>, panel_xhy_upd_rs<7>, panel_xhy_upd_rs<8>};   // by column blocks of 16
         const int KP = (k + 15) / 16;
-        const int64_t gr = grid_blocks(ntiles, c->num_cu);
-        if (c->xhy.capacity() < 2 * sect + npart_n + 2 * gr * nslots)
-            return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld)", (long long)c->xhy.capacity());
-        const size_t ldsr = (size_t)4 * (KP * 4096 + 8192);
+        const int gr = grid_blocks(ntiles, c->num_cu);
+        if (!ws.holds(2 * gr)) return fail(LK_ERR_INVALID, "internal: xhy workspace too small for the fused block pass (%lld)", (long long)c->xhy.capacity());
         {
             ProfScope ps(c, "xhy_upd_mfma", (double)Bx->n * 8.0 * (k + 2 * p));
-            auto go = [&](auto kern) -> int {
-                if (ldsr > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
-                hipLaunchKernelGGL(kern, dim3((unsigned)gr), dim3(512), ldsr, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld, p, Bx->n, H1dev, part,
-                                   npart, c->guard());
-                return LK_OK;
-            };
-            switch (KP) {
-            case 1: LKCHK(go(&panel_xhy_upd_rs<1>)); break;
-            case 2: LKCHK(go(&panel_xhy_upd_rs<2>)); break;
-            case 3: LKCHK(go(&panel_xhy_upd_rs<3>)); break;
-            case 4: LKCHK(go(&panel_xhy_upd_rs<4>)); break;
-            case 5: LKCHK(go(&panel_xhy_upd_rs<5>)); break;
-            case 6: LKCHK(go(&panel_xhy_upd_rs<6>)); break;
-            case 7: LKCHK(go(&panel_xhy_upd_rs<7>)); break;
-            default: LKCHK(go(&panel_xhy_upd_rs<8>)); break;
-            }
+            LKCHK(launch_lds(UPD_RS[std::min(KP, 8) - 1], dim3(gr), dim3(512), (size_t)4 * (KP * 4096 + 8192), c->stream, Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld,
+                             p, Bx->n, H1dev, ws.part(), ws.npart(), c->guard()));
         }
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part, (int)(2 * gr), npart, (int)(2 * gr), k, p, ED, 0, out);
-        HIPCHK(hipGetLastError());
-        if (out_dev) *out_dev = out;
-        return allreduce(c, out, nslots);
+        return finish_xhy_step(c, ws, 2 * gr, 2 * gr, k, p, ED, 0, slot, out_dev);
     }
     const size_t lds = (size_t)(KG * 32 * 34 + 32 * 34 + KG * 32 * 34 * (cp ? 2 : 1)) * sizeof(double);
     {
         ProfScope ps(c, "xhy_upd_mfma", (double)Bx->n * ED * 8.0 * (k + 2 * p));
-        auto go = [&](auto kern) -> int {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld, p, Bx->n,
-                               H1dev, part, npart, c->gemm_store_policy | (c->upd_debug << 4), c->guard());
-            return LK_OK;
-        };
-        if (cp) LKCHK(go(&panel_xhy_upd_mfma<true>));
-        else LKCHK(go(&panel_xhy_upd_mfma<false>));
+        LKCHK(launch_lds(cp ? panel_xhy_upd_mfma<true> : panel_xhy_upd_mfma<false>, dim3(grid), dim3(256), lds, c->stream, Bx->col(c0), Bx->ld, k, By->col(jy0), By->ld, p, Bx->n,
+                         H1dev, ws.part(), ws.npart(), c->gemm_store_policy | (c->upd_debug << 4), c->guard()));
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(finish_xhy, dim3((unsigned)((nslots + 15) / 16)), dim3(256), 0, c->stream, part, grid, npart, grid, k, p, ED, 0, out);
-    HIPCHK(hipGetLastError());
-    if (out_dev) *out_dev = out;
-    return allreduce(c, out, nslots);
+    return finish_xhy_step(c, ws, grid, grid, k, p, ED, 0, slot, out_dev);
 }
 
 // ---- tall-skinny product launcher (panel_gemm) -------------------------------------------------------------
@@ -915,7 +870,12 @@ int gemm_launch_valu(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q
     const bool cp = Bx->dtype == LK_C128;
     const int ED = Bx->ed();
     // accumulators per lane: the smallest of 1 / 2 / 4 / 8 / 16 that holds the product (q <= 16), 16 beyond
-    const int QB = q <= 1 ? 1 : (q <= 2 ? 2 : (q <= 4 ? 4 : (q <= 8 ? 8 : GEMM_QB)));
+    const int lq = q <= 1 ? 0 : (q <= 2 ? 1 : (q <= 4 ? 2 : (q <= 8 ? 3 : 4))), QB = 1 << lq;
+    // columns in flight per lane: 16 (real) / 8 (complex) loads of 16 B for the narrow shapes, half that beside 8-16 accumulators
+    static const decltype(&panel_gemm<false, 16, 1>) PANEL_GEMM[2][5] = {
+        {panel_gemm<false, 16, 1>, panel_gemm<false, 16, 2>, panel_gemm<false, 16, 4>, panel_gemm<false, 8, 8>, panel_gemm<false, 8, GEMM_QB>},
+        {panel_gemm<true, 8, 1>, panel_gemm<true, 8, 2>, panel_gemm<true, 8, 4>, panel_gemm<true, 4, 8>, panel_gemm<true, 4, GEMM_QB>},
+    };
     const int total = ((q + QB - 1) / QB) * k * QB * ED;
     hipLaunchKernelGGL(pack_coef, dim3((total + 255) / 256 > 64 ? 64 : (total + 255) / 256), dim3(256), 0, c->stream, Cdev, ldc, k, q,
                        QB, ED, sign, pack);
@@ -928,28 +888,8 @@ int gemm_launch_valu(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q
         const int g = grid_blocks((Bx->n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * c->gemm_grid_mult);
         const double *Cp = pack + (int64_t)(q0 / QB) * k * QB * ED;
         ProfScope ps(c, "lincomb", (double)Bx->n * ED * 8.0 * (k + qn * (accumulate ? 2 : 1)));
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0 + q0), By->ld, qn,
-                               Cp, Bx->n, accumulate, QGB, c->gemm_store_policy, c->guard());
-        };
-        // columns in flight per lane: 16 (real) / 8 (complex) loads of 16 B for the narrow shapes, half that beside 8-16 accumulators
-        if (cp) {
-            switch (QB) {
-            case 1: go(&panel_gemm<true, 8, 1>); break;
-            case 2: go(&panel_gemm<true, 8, 2>); break;
-            case 4: go(&panel_gemm<true, 8, 4>); break;
-            case 8: go(&panel_gemm<true, 4, 8>); break;
-            default: go(&panel_gemm<true, 4, GEMM_QB>);
-            }
-        } else {
-            switch (QB) {
-            case 1: go(&panel_gemm<false, 16, 1>); break;
-            case 2: go(&panel_gemm<false, 16, 2>); break;
-            case 4: go(&panel_gemm<false, 16, 4>); break;
-            case 8: go(&panel_gemm<false, 8, 8>); break;
-            default: go(&panel_gemm<false, 8, GEMM_QB>);
-            }
-        }
+        hipLaunchKernelGGL(PANEL_GEMM[cp][lq], dim3(g), dim3(256), 0, c->stream, (const double *)Bx->col(c0), Bx->ld, k, By->col(jy0 + q0), By->ld, qn,
+                           Cp, Bx->n, accumulate, QGB, c->gemm_store_policy, c->guard());
         HIPCHK(hipGetLastError());
     }
     return LK_OK;
@@ -960,43 +900,26 @@ int gemm_launch_valu(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q
 template <bool CPLX, int NG>
 int gemm_mfma_one(lk_context_t c, const double *X, int64_t ldx, int kk, double *Y, int64_t ldy, int qn, const double *Cp, int64_t n,
                   int accumulate) {
-    const int nt = (kk + 3) / 4;
-    const size_t lds = (size_t)NG * nt * 64 * sizeof(double);
-    if (lds > 48 * 1024)                         // more than the default dynamic-LDS limit needs the opt-in (gfx950: 160 KB per workgroup)
-    {
-        if constexpr (!(CPLX && NG >= 8))
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma<CPLX, NG, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma<CPLX, NG, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    const size_t lds = (size_t)NG * ((kk + 3) / 4) * 64 * sizeof(double);
     constexpr int tile_rows = 8 * 2 * (CPLX ? 16 : 32);
     const int g = grid_blocks((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * (NG >= 8 ? 1 : (NG >= 4 && CPLX ? 2 : c->gemm_grid_mult)));
+    auto kern = panel_gemm_mfma<CPLX, NG, false, false>;        // the batch schedule
+    bool prefetch_y = false;
     if constexpr (!CPLX && NG <= 2) {
-        if (accumulate && c->gemm_prefetch_y) {          // the accumulating update of the block Gram-Schmidt: Y's tile loaded ahead of the k-loop
-            if (lds > 48 * 1024)
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma<CPLX, NG, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            // (the rolling prefetch of X beside the prefetched tile of Y does not fit the register file: batch schedule here)
-            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, true, false>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
-                               c->gemm_store_policy, c->guard());
-            HIPCHK(hipGetLastError());
-            return LK_OK;
-        }
+        // the accumulating update of the block Gram-Schmidt: Y's tile loaded ahead of the k-loop
+        // (the rolling prefetch of X beside the prefetched tile of Y does not fit the register file: batch schedule here)
+        prefetch_y = accumulate && c->gemm_prefetch_y;
+        if (prefetch_y) kern = panel_gemm_mfma<CPLX, NG, true, false>;
     }
-    constexpr bool CAN_ROLL = !(CPLX && NG >= 8);          // (64 complex outputs as the doubled real problem: the ring does not fit the register file)
-    bool rolled = false;
-    if constexpr (CAN_ROLL) {
+    if constexpr (!(CPLX && NG >= 8)) {                    // (64 complex outputs as the doubled real problem: the ring does not fit the register file)
         // "gemm_roll" = 1 (default): the real product with 33..64 outputs per pass -- the restart update X <- X Z of krylov_schur -- on the straight-line
         // ring (k = 128, q = 64 at n = 10^7: 3.45-3.73 -> 3.16-3.24 ms, 51 TFLOP/s); the narrower ones measured the same on either schedule
         // (k = 64, q = 32: 1.38-1.44 ms both) and keep the batch schedule's three blocks per CU; 2 = every variant that has a ring
         // (the real kind's straight-line ring is unrolled for the basis widths 128 and 64: any other width keeps the batch schedule)
-        if ((CPLX || kk == 128 || kk == 64) && (c->gemm_roll >= 2 || (c->gemm_roll == 1 && !CPLX && NG == 4))) {
-            hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, true>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
-                               c->gemm_store_policy, c->guard());
-            rolled = true;
-        }
+        if (!prefetch_y && (CPLX || kk == 128 || kk == 64) && (c->gemm_roll >= 2 || (c->gemm_roll == 1 && !CPLX && NG == 4)))
+            kern = panel_gemm_mfma<CPLX, NG, false, true>;
     }
-    if (!rolled)
-        hipLaunchKernelGGL((panel_gemm_mfma<CPLX, NG, false, false>), dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
-                           c->gemm_store_policy, c->guard());
+    LKCHK(launch_lds(kern, dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate, c->gemm_store_policy, c->guard()));
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -1005,46 +928,35 @@ int gemm_mfma_one(lk_context_t c, const double *X, int64_t ldx, int kk, double *
 template <int NG, int NR = (NG >= 4 ? 1 : 2)>
 int gemm_mfma3m_one(lk_context_t c, const double *X, int64_t ldx, int kk, double *Y, int64_t ldy, int qn, const double *Cp, int64_t n,
                     int accumulate) {
-    const int nt = (kk + 3) / 4;
-    const size_t lds = (size_t)NG * nt * 128 * sizeof(double);
+    const size_t lds = (size_t)NG * ((kk + 3) / 4) * 128 * sizeof(double);
     const bool roll = c->gemm_roll >= 1 && (kk == 128 || kk == 64);       // "gemm_roll": see gemm_mfma_one (the complex kind: every width of product measured faster on the ring)
-    if (lds > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma3m<NG, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&panel_gemm_mfma3m<NG, NR, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     constexpr int tile_rows = 8 * NR * 16;
     const int g = grid_blocks((n + tile_rows - 1) / tile_rows, (int64_t)c->num_cu * (NG >= 4 ? 2 : (NG >= 2 ? 2 : c->gemm_grid_mult)));
-    const auto kern = roll ? panel_gemm_mfma3m<NG, NR, true> : panel_gemm_mfma3m<NG, NR>;
-    hipLaunchKernelGGL(kern, dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate, c->gemm_store_policy, c->guard());
+    LKCHK(launch_lds(roll ? panel_gemm_mfma3m<NG, NR, true> : panel_gemm_mfma3m<NG, NR>, dim3(g), dim3(512), lds, c->stream, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate,
+                     c->gemm_store_policy, c->guard()));
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
 
-int gemm_launch_mfma3m(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q, const double *Cdev, int64_t ldc, double sign,
-                       int accumulate, double *pack) {
+// The schedule of either matrix-core product: k-chunks of KMAX_FUSED columns -- `pack_chunk(grid, kc, kk)` packs a chunk's coefficient tiles, `step` doubles per group
+// of QB outputs and k-step of 4 columns --, and within a chunk launches of up to NGMAX output groups: `one(groups, X, ldx, kk, Y, ldy, qn, Cp, n, accumulate)`.
+template <class Pack, class One>
+int gemm_chunk_loop(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q, int accumulate, const double *pack, int QB, int NGMAX, int step, Pack &&pack_chunk,
+                    One &&one) {
     lk_context_t c = Bx->ctx;
-    constexpr int QB = 16, NGMAX = 4;
+    const int ngroups = (q + QB - 1) / QB;
     for (int kc = 0; kc < k; kc += KMAX_FUSED) {
-        const int kk = (k - kc) < KMAX_FUSED ? (k - kc) : KMAX_FUSED;
+        const int kk = std::min(k - kc, KMAX_FUSED);
         const int nt = (kk + 3) / 4;
-        const int ngroups = (q + QB - 1) / QB;
-        const int total = ngroups * nt * 128;
-        hipLaunchKernelGGL(pack_coef_mfma3m, dim3((total + 255) / 256 > 64 ? 64 : (total + 255) / 256), dim3(256), 0, c->stream,
-                           Cdev + (int64_t)kc * 2, ldc, kk, q, sign, pack);
+        const int total = ngroups * nt * step;
+        pack_chunk(dim3(std::min((total + 255) / 256, 64)), kc, kk);
         HIPCHK(hipGetLastError());
         const int acc = (accumulate || kc > 0) ? 1 : 0;
         for (int g0 = 0; g0 < ngroups; g0 += NGMAX) {
-            const int groups = (ngroups - g0) < NGMAX ? (ngroups - g0) : NGMAX;
-            const int qn = (q - g0 * QB) < groups * QB ? (q - g0 * QB) : groups * QB;
-            const double *Cp = pack + (int64_t)g0 * nt * 128;
-            const double *Xp = Bx->col(c0 + kc);
-            double *Yp = By->col(jy0 + g0 * QB);
-            ProfScope ps(c, "lincomb", (double)Bx->n * 16.0 * (kk + qn * (acc ? 2 : 1)));
-            int rc;
-            if (groups <= 1) rc = gemm_mfma3m_one<1>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-            else if (groups == 2) rc = gemm_mfma3m_one<2>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-            else rc = gemm_mfma3m_one<4>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-            LKCHK(rc);
+            const int groups = std::min(ngroups - g0, NGMAX);
+            const int qn = std::min(q - g0 * QB, groups * QB);
+            ProfScope ps(c, "lincomb", (double)Bx->n * Bx->ed() * 8.0 * (kk + qn * (acc ? 2 : 1)));
+            LKCHK(one(groups, Bx->col(c0 + kc), Bx->ld, kk, By->col(jy0 + g0 * QB), By->ld, qn, pack + (int64_t)g0 * nt * step, Bx->n, acc));
         }
     }
     return LK_OK;
@@ -1055,39 +967,21 @@ int gemm_launch_mfma(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q
     lk_context_t c = Bx->ctx;
     const bool cp = Bx->dtype == LK_C128;
     const int ED = Bx->ed();
-    if (cp && c->gemm_3m) return gemm_launch_mfma3m(Bx, c0, k, By, jy0, q, Cdev, ldc, sign, accumulate, pack);
-    const int QB = cp ? 8 : 16, NGMAX = cp ? 8 : 4;
-    for (int kc = 0; kc < k; kc += KMAX_FUSED) {
-        const int kk = (k - kc) < KMAX_FUSED ? (k - kc) : KMAX_FUSED;
-        const int nt = (kk + 3) / 4;
-        const int ngroups = (q + QB - 1) / QB;
-        const int total = ngroups * nt * 64;
-        hipLaunchKernelGGL(pack_coef_mfma, dim3((total + 255) / 256 > 64 ? 64 : (total + 255) / 256), dim3(256), 0, c->stream,
-                           Cdev + (int64_t)kc * ED, ldc, kk, q, cp ? 1 : 0, sign, pack);
-        HIPCHK(hipGetLastError());
-        const int acc = (accumulate || kc > 0) ? 1 : 0;
-        for (int g0 = 0; g0 < ngroups; g0 += NGMAX) {
-            const int groups = (ngroups - g0) < NGMAX ? (ngroups - g0) : NGMAX;
-            const int qn = (q - g0 * QB) < groups * QB ? (q - g0 * QB) : groups * QB;
-            const double *Cp = pack + (int64_t)g0 * nt * 64;
-            const double *Xp = Bx->col(c0 + kc);
-            double *Yp = By->col(jy0 + g0 * QB);
-            ProfScope ps(c, "lincomb", (double)Bx->n * ED * 8.0 * (kk + qn * (acc ? 2 : 1)));
-            int rc;
-            if (cp) {
-                if (groups <= 1) rc = gemm_mfma_one<true, 1>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-                else if (groups == 2) rc = gemm_mfma_one<true, 2>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-                else if (groups <= 4) rc = gemm_mfma_one<true, 4>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-                else rc = gemm_mfma_one<true, 8>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-            } else {
-                if (groups <= 1) rc = gemm_mfma_one<false, 1>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-                else if (groups == 2) rc = gemm_mfma_one<false, 2>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-                else rc = gemm_mfma_one<false, 4>(c, Xp, Bx->ld, kk, Yp, By->ld, qn, Cp, Bx->n, acc);
-            }
-            LKCHK(rc);
-        }
-    }
-    return LK_OK;
+    if (cp && c->gemm_3m)       // groups of 16 complex outputs, up to 4 per launch, separate real / imaginary coefficient tiles
+        return gemm_chunk_loop(Bx, c0, k, By, jy0, q, accumulate, pack, 16, 4, 128,
+            [&](dim3 grid, int kc, int kk) { hipLaunchKernelGGL(pack_coef_mfma3m, grid, dim3(256), 0, c->stream, Cdev + (int64_t)kc * 2, ldc, kk, q, sign, pack); },
+            [&](int groups, auto... a) {
+                return groups <= 1 ? gemm_mfma3m_one<1>(c, a...) : (groups == 2 ? gemm_mfma3m_one<2>(c, a...) : gemm_mfma3m_one<4>(c, a...));
+            });
+    // groups of 16 real / 8 complex outputs, up to 4 / 8 per launch
+    return gemm_chunk_loop(Bx, c0, k, By, jy0, q, accumulate, pack, cp ? 8 : 16, cp ? 8 : 4, 64,
+        [&](dim3 grid, int kc, int kk) { hipLaunchKernelGGL(pack_coef_mfma, grid, dim3(256), 0, c->stream, Cdev + (int64_t)kc * ED, ldc, kk, q, cp ? 1 : 0, sign, pack); },
+        [&](int groups, auto... a) {
+            if (cp)
+                return groups <= 1 ? gemm_mfma_one<true, 1>(c, a...)
+                                   : (groups == 2 ? gemm_mfma_one<true, 2>(c, a...) : (groups <= 4 ? gemm_mfma_one<true, 4>(c, a...) : gemm_mfma_one<true, 8>(c, a...)));
+            return groups <= 1 ? gemm_mfma_one<false, 1>(c, a...) : (groups == 2 ? gemm_mfma_one<false, 2>(c, a...) : gemm_mfma_one<false, 4>(c, a...));
+        });
 }
 
 int gemm_launch(lk_basis_t Bx, int c0, int k, lk_basis_t By, int jy0, int q, const double *Cdev, int64_t ldc, double sign,
