@@ -1116,7 +1116,8 @@ contains
     !> the panel Bx (initial guess, overwritten) with b = column jb of Bb.  V: the caller's workspace panel of at least kdim + 1 columns,
     !> kdim + 2 with a preconditioner.  precond: a RIGHT preconditioner given as an engine operator (e.g. a diagonal operator holding
     !> 1 / diag(A)); absent = none.  rtol, atol, kdim and maxiter default to the reference's (rtol_dp, atol_dp, 30, 10).  info = +n_iter
-    !> converged, -n_iter not.  res (optional) receives the residual history up to its size, nres its full length.
+    !> converged, -n_iter not; info = 0 (nres = 1, res(1) = 0, x as it came): the start residual is exactly zero, x solves the system
+    !> already (gmres.fypp:142-143 divide by it).  res (optional) receives the residual history up to its size, nres its full length.
     subroutine gpu_gmres_rdp(op, Bb, jb, Bx, jx, V, info, rtol, atol, precond, kdim, maxiter, trans, res, nres, n_inner, n_outer)
         type(c_ptr), intent(in) :: op, Bb, Bx, V
         integer, intent(in) :: jb, jx

@@ -561,7 +561,8 @@ module lightkrylov_hip_c
         end function
         !> restarted GMRES(kdim) as one call (gmres.fypp:65-255): op(A) x = b, x = column jx of Bx (initial guess, overwritten), b =
         !> column jb of Bb; M = c_null_ptr or a right preconditioner (an engine operator); V = workspace of >= kdim + 1 columns (kdim + 2
-        !> with M).  res: res_cap entries of the residual history at most, nres its full length
+        !> with M).  res: res_cap entries of the residual history at most, nres its full length.  info = +n_iter converged, -n_iter not,
+        !> 0 with nres = 1 and res(1) = 0 when the start residual is exactly zero: x is left as it came (the reference returns NaN)
         function lk_gmres(A, trans, M, Bb, jb, Bx, jx, V, rtol, atol, kdim, maxiter, res, res_cap, nres, n_inner, n_outer, info) &
             bind(C, name="lk_gmres") result(rc)
             import :: c_int, c_ptr, c_double, c_int64_t

@@ -581,6 +581,13 @@ int lk_kexpm_block(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t B
  * x += dx.  The cycle ends with lk_linop_residual into V(:, 0) and its norm (:205-214); when the solve goes on, the NEXT cycle
  * normalises THIS vector instead of forming it again (:134-142 compute the same vector the same way): the call applies ONE PRODUCT
  * FEWER PER RESTART than the reference's loop counts, and three passes fewer.
+ * A START RESIDUAL OF EXACTLY ZERO (x the exact solution already -- a warm start from a converged step --, or b = 0 with x = 0): the
+ * reference divides by beta = 0 (gmres.fypp:142-143) and returns NaN.  Here the call returns LK_OK with x unchanged, info = 0,
+ * n_inner = n_outer = 0, nres = 1 and res[0] = 0, for both kinds, with or without M, whatever atol is; columns of V the call may write
+ * are written.  beta reaches the host with the first delivery anyway: the case costs no synchronisation on any other path.  A residual
+ * below tol that is not zero takes one step, as in the reference.  This covers the residual the call STARTS from.  With tol = 0 (rtol = atol = 0,
+ * or b = 0 with atol = 0 and x != 0) no residual counts as converged, a zero one included: a later cycle that starts from a residual of
+ * exactly zero ends in LK_ERR_INVALID "TRTRS failed" (real kind, a zero pivot) or LK_ERR_NAN (complex kind, the rotation divides by it).
  * info = +n_iter when converged, -n_iter otherwise (:234-238); n_iter counts the inner steps plus one per cycle.  res (may be NULL)
  * receives at most res_cap entries of the residual history, nres its full length, at most 1 + (maxiter + 1)(kdim + 1); n_inner and
  * n_outer as in gmres_dp_metadata (IterativeSolvers.fypp:153-170).  nres, n_inner and n_outer may be NULL.

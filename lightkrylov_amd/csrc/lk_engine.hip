@@ -3843,6 +3843,7 @@ struct GmresState {
     int last = 0;                     // last step of this cycle that has been rotated
     double hsub = 0.0;                // H(last + 1, last) as the step delivered it
     bool converged = false;
+    bool zero_start = false;          // ||r0|| of the first cycle is exactly zero: x solves the system as it stands, no step counts
     int n_iter = 0, n_inner = 0;
     int rc = LK_OK;
     // gmres.fypp:178-195 for step k; true when |e(k+1)| < tol
@@ -3875,6 +3876,8 @@ int gmres_progress(void *user, int kfirst, int klast) {
         if (!std::isfinite(beta)) { st.rc = fail(LK_ERR_NAN, "lk_gmres: the residual norm is not finite"); return 1; }
         st.e[0] = beta;
         st.res.push_back(beta);
+        // the reference divides by beta here (:142-143) and returns NaN; the step delivered with it ran on the zero vector and is dropped
+        if (beta == 0.0) { st.zero_start = true; return 1; }
     }
     for (int k = kfirst; k <= klast; ++k)
         if (st.step(k)) return 1;
@@ -3926,12 +3929,14 @@ static int gmres_impl(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int 
         } else {
             st.e[0] = beta;     // V(1) is the residual the last cycle ended with (:205-214), the same vector :134-142 would form again
         }
-        // V(1) / beta in place, beta read on the device (:143); a zero residual is left as it is and ends the cycle at its first step
+        // V(1) / beta in place, beta read on the device (:143); a zero residual is left as it is and ends the batch at its first step, whose
+        // delivery brings beta = 0 to the host: the call ends there (zero_start)
         LKCHK(scal_launch(V, 0, 1.0, 0.0, c->red, std::numeric_limits<double>::min()));
         st.last = 0;
         int ainfo = 0;
         LKCHK(arnoldi_impl(op, &Xv, H.data(), ldh, 1, kdim, tol, op_trans, &ainfo, segs.data(), kdim, gmres_progress, &st));   // :155-195
         LKCHK(st.rc);
+        if (st.zero_start) break;                                // info = 0, no iteration, the history is [0], x as it came
         if (st.last < 1) return fail(LK_ERR_INVALID, "internal: lk_gmres saw no Arnoldi step");
         // the batch ended on H(k+1, k) <= tol with the residual still above it: the reference goes on with the unscaled vector (:171-172).
         // arnoldi has normalised the vector of the step it stopped at, as its qr does down to atol_dp (qr.fypp:164): undone here, to rounding

@@ -145,7 +145,8 @@ def _gmres_engine(A, b, x, rtol, atol, M, kdim, maxiter, transpose, meta) -> int
     if meta is not None:
         meta.n_iter, meta.n_inner, meta.n_outer = abs(info.value), n_inner.value, n_outer.value
         meta.res = [float(r) for r in res[:nres.value]]
-        meta.converged, meta.info = info.value > 0, info.value
+        # info = 0: a start residual of exactly zero (nres = 1, res[0] = 0), x solves the system as it came
+        meta.converged, meta.info = info.value > 0 or (info.value == 0 and nres.value == 1), info.value
     A.reset_counter(transpose, "gmres%post")
     return info.value
 
@@ -155,7 +156,8 @@ def gmres(A: abstract_linop, b: abstract_vector, x: abstract_vector, rtol: float
           transpose: bool = False, meta: gmres_dp_metadata | None = None, engine: bool | None = None) -> int:
     """Restarted GMRES(kdim).  src/IterativeSolvers/GMRES/gmres.fypp:65-255.
     x is the initial guess and is overwritten by the solution.  Returns info = +n_iter if
-    converged, -n_iter otherwise (:234-238); `meta` (if given) receives the residual history.
+    converged, -n_iter otherwise (:234-238); `meta` (if given) receives the residual history.  A start residual of exactly zero
+    returns info = 0 with `meta.converged`, the history [0.0] and x untouched (the reference divides by it, :142-143).
     `engine` (engine extra): the whole solve as one lk_gmres call.  None takes it exactly when the preconditioner is a
     `linop_precond_gpu`, A an engine operator, the vectors GPU vectors and the context has one rank; True asks for it on an
     unpreconditioned solve as well (and raises where it cannot be had); False never.  Unpreconditioned solves without the keyword
@@ -188,6 +190,12 @@ def gmres(A: abstract_linop, b: abstract_vector, x: abstract_vector, rtol: float
         e = np.zeros(kdim + 1, dtype=dt)
         beta = V[0].norm()
         e[0] = beta
+        if m.n_outer == 0 and beta == 0.0:
+            # a start residual of exactly zero (x solves the system already, or b = 0 with x = 0): :143 divides by it and the reference
+            # returns NaN.  lk_gmres' answer: info = 0, converged, no iteration, the history [0], x as it came
+            m.res = [0.0]
+            m.converged = True
+            break
         V[0].scal(1.0 / beta)
         c = np.zeros(kdim, dtype=dt)
         s = np.zeros(kdim, dtype=dt)

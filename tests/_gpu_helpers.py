@@ -221,9 +221,10 @@ class CallerPanel:
     """An n x ncols panel wrapped (lk_basis_wrap) inside one flat engine-owned buffer laid out as `layout` says.  `set` writes panel
     contents, `get` reads them back and asserts that nothing outside the panel's rows changed.  The layouts (tests/test_gpu_caller_memory.py):
     "nan_pad" / "big_pad" ld = n + 3 or n + 4 with NaN / +-1e300 padding, "offNNN" the same ld NNN bytes into a buffer of live non-zero
-    rows, "unpadded" ld = n; `extra_ld` (even) more padding rows per column, for two panels of one shape with different ld."""
+    rows, "unpadded" ld = n; `extra_ld` (even) more padding rows per column, for two panels of one shape with different ld; `pad`: ld = n + pad
+    exactly, for either kind (the caller keeps ld even for the real kind)."""
 
-    def __init__(self, ctx, dtype, n, ncols, layout, seed=0, extra_ld=0):
+    def __init__(self, ctx, dtype, n, ncols, layout, seed=0, extra_ld=0, pad=None):
         dt = np.dtype(dtype)
         cplx = dt.kind == "c"
         es = dt.itemsize
@@ -231,7 +232,8 @@ class CallerPanel:
             assert (n % 2 == 1) == cplx, "fit() the size first"
             ld, head = n, 16 // es
         else:
-            ld = n + (3 if cplx else 3 + (n + 3) % 2) + extra_ld
+            ld = n + (3 if cplx else 3 + (n + 3) % 2) + extra_ld if pad is None else n + pad
+            assert cplx or ld % 2 == 0
             head = int(layout[3:]) // es if layout.startswith("off") else 0
         total = head + ld * ncols + 64
         img = np.empty(total, dtype=dt)

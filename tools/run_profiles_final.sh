@@ -15,9 +15,11 @@ B="python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
 # -- 1. HBM traffic of the three DGS sweeps: the single-GPU workload and rank 0's row block of the 2 / 4 / 8-rank jobs (one record per n_local)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_fetch" -o bench -- $B > "$D/pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$D/pmc_write" -o bench -- $B > "$D/pmc_write.log" 2>&1
+# (a rank of a P-rank job has a communicator and never looks ahead; its row block alone on a GPU would: the shard passes run the three sweeps,
+#  "fuse_rowop" = 1 -- the command tools/make_profiles.py writes into the record)
 for P in 2 4 8; do
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_fetch_s$P" -o bench -- $B --shard-of $P > "$D/pmc_fetch_s$P.log" 2>&1
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$D/pmc_write_s$P" -o bench -- $B --shard-of $P > "$D/pmc_write_s$P.log" 2>&1
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$D/pmc_fetch_s$P" -o bench -- $B --shard-of $P --tune fuse_rowop=1 > "$D/pmc_fetch_s$P.log" 2>&1
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$D/pmc_write_s$P" -o bench -- $B --shard-of $P --tune fuse_rowop=1 > "$D/pmc_write_s$P.log" 2>&1
 done
 (cd "$R" && python3 tools/make_profiles.py "$D" onbox > "$D/make_profiles_onbox.log" 2>&1)     # profiles/pmc_traffic.json of THIS build, on the box
 # -- 2. the bench lines (now with `traffic`), the kernel trace, the shard lines, the 8-process line
