@@ -17,6 +17,14 @@
  *     data[j * ld + i]; ld is padded so every column starts 256-byte aligned.
  *     A single vector is a 1-column basis; every vector argument is a (basis, column) pair
  *     with 0-based column indices.
+ *   - "the same memory" is judged by DEVICE ADDRESS, never by handle: a second handle onto a panel
+ *     (lk_basis_wrap at the address of one of its columns: a view) names the same columns.  A column
+ *     owns the bytes of its rows [0, n_local) and nothing else; two column sets OVERLAP when a column
+ *     of the one meets a column of the other, in whole or in part.  The padding rows [n_local, ld)
+ *     belong to nobody: another panel may live in them.  A call that writes refuses (LK_ERR_INVALID,
+ *     nothing written) an output that overlaps an input it still reads; the exact same column is
+ *     the in-place case where an entry has one (lk_vec_axpby, lk_vec_copy's no-op).  Calls that only
+ *     read (lk_vec_dot, lk_innerprod, lk_gram) take any overlap.
  *   - dtype LK_F64  = real(dp)     (reference kind "rdp")
  *           LK_C128 = complex(dp)  (reference kind "cdp"), interleaved (re, im).
  *     Scalars cross the ABI as `const double*` to 1 (F64) or 2 (C128) doubles.
@@ -219,7 +227,9 @@ int lk_profile_reset(lk_context_t ctx);
  * IterativeSolvers.fypp:1032-1034): n_local rows on this rank, columns zero-filled. */
 int lk_basis_create(lk_context_t ctx, int dtype, int64_t n_local, int ncols, lk_basis_t *B);
 /* wrap caller-owned device memory (e.g. a torch tensor).  ld in elements; dev_ptr 16-byte
- * aligned; ld even for LK_F64.  Rows [n_local, ld) are never read or written. */
+ * aligned; ld even for LK_F64.  Rows [n_local, ld) are never read or written.  This is also how
+ * a VIEW of columns [j, j + ncols) of a panel is made (same ld, dev_ptr = the address of column j):
+ * every entry treats view and parent as the same memory (the overlap rule under "Model"). */
 int lk_basis_wrap(lk_context_t ctx, int dtype, int64_t n_local, int ncols, int64_t ld,
                   void *dev_ptr, lk_basis_t *B);
 int lk_basis_destroy(lk_basis_t B);

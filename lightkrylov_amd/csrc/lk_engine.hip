@@ -170,7 +170,10 @@ struct lk_context_s {
     int lazy = 0;
     struct {
         bool valid = false;
+        // Memos, queue and speculation name a column by its device ADDRESS: (xbase, xld) is the lattice xbase + i * xld * ed the
+        // columns lie on, j0 / cnt / jy index it, and col_index() finds the index of a column of ANY handle onto the same memory.
         const double *xbase = nullptr;   // panel the memoised columns live in
+        int64_t xld = 0;
         const double *y = nullptr;       // the vector they were dotted with
         int j0 = 0, cnt = 0;
         std::vector<double> vals;
@@ -181,10 +184,10 @@ struct lk_context_s {
     struct {
         bool valid = false;
         const double *xbase = nullptr;
+        int64_t xld = 0;
         int cnt = 0;
         std::vector<double> G;           // [j][i][ED] = conj(X_i) . X_j
-        const double *last_x = nullptr;  // the previous in-panel dot call (pattern detection)
-        int last_jx = -1, last_jy = -1;
+        const double *last_x = nullptr, *last_y = nullptr;  // the columns of the previous in-panel dot call (pattern detection)
     } gmemo;
     void forget_memos() { memo.valid = false; nmemo.valid = false; gmemo.valid = false; gmemo.last_x = nullptr; }
     // queue: pending  T <- [zeroed ? 0 : T] + sum_i a_i X(:, j0+i)  (linear_combination's loop).  `zeroed`: the queue
@@ -214,6 +217,7 @@ struct lk_context_s {
     // A prediction nobody used (no dot of the batch was asked for before the next one) disarms it: at most one wasted sweep.
     struct {
         const double *xbase = nullptr;   // panel the pattern was seen on
+        int64_t xld = 0;
         int jy = -1, j0 = 0;             // ... for this column, against the columns [j0, jy)
         bool armed = false, unused = false;
         const double *last_norm_y = nullptr;   // the vector whose norm was the previous lazy-mode call (plain kernel)
@@ -398,6 +402,59 @@ int check_pair(lk_basis_t A, lk_basis_t B, const char *what) {
     if (A->n != B->n) return fail(LK_ERR_INVALID, "%s: Inconsistent size between the two vectors (%lld vs %lld)", what,
                                   (long long)A->n, (long long)B->n);
     return LK_OK;
+}
+
+// ---- the one overlap rule ----------------------------------------------------------------------------------------------------------------
+// "Is this the same memory?" is decided by DEVICE ADDRESS, never by handle: a second handle (lk_basis_wrap at col(j) of a panel, a view)
+// reaches the same columns.  A column owns the bytes of its rows [0, n) and nothing else -- the padding rows [n, ld) belong to nobody, so
+// another panel may live in them.  Two column sets overlap when some column of the one meets some column of the other.
+struct ColSet {
+    intptr_t p;            // address of the first column (bytes)
+    int64_t stride, w;     // bytes from one column to the next; bytes of one column's rows [0, n)
+    int cnt;
+};
+inline ColSet colset(lk_basis_t B, int j0, int cnt) {
+    return ColSet{(intptr_t)B->col(j0), B->ld * B->ed() * (int64_t)sizeof(double), B->n * B->ed() * (int64_t)sizeof(double), cnt};
+}
+inline int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }
+bool cols_overlap(ColSet a, ColSet b) {
+    if (a.cnt < 1 || b.cnt < 1 || a.w < 1 || b.w < 1) return false;
+    // the hulls first: four compares settle every call whose operands lie apart (each step of a factorisation, y behind X(:, :k))
+    if (a.p + (a.cnt - 1) * a.stride + a.w <= b.p || b.p + (b.cnt - 1) * b.stride + b.w <= a.p) return false;
+    if (a.cnt > b.cnt) std::swap(a, b);
+    // column x of the smaller set meets column j of the other when  b.p + j s < x + a.w  and  x < b.p + j s + b.w: the uniform stride
+    // gives the range of such j without walking the second set
+    for (int i = 0; i < a.cnt; ++i) {
+        const int64_t d = (int64_t)(a.p + (int64_t)i * a.stride - b.p);
+        if (b.cnt == 1 || b.stride < 1) {
+            if (d + a.w > 0 && d < b.w) return true;
+            continue;
+        }
+        int64_t jlo = floor_div(d - b.w, b.stride) + 1, jhi = floor_div(d + a.w - 1, b.stride);
+        if (jlo < 0) jlo = 0;
+        if (jhi > b.cnt - 1) jhi = b.cnt - 1;
+        if (jlo <= jhi) return true;
+    }
+    return false;
+}
+inline bool cols_overlap(lk_basis_t A, int ja, int na, lk_basis_t B, int jb, int nb) { return cols_overlap(colset(A, ja, na), colset(B, jb, nb)); }
+// Both handles step through the same memory with the same stride: column j of Y is column j + *shift of X (which may lie outside X's range).
+inline bool same_columns(lk_basis_t Bx, lk_basis_t By, int64_t *shift) {
+    const int64_t stride = Bx->ld * Bx->ed() * (int64_t)sizeof(double);
+    if (Bx->ld != By->ld || Bx->dtype != By->dtype || stride < 1) return false;
+    const int64_t d = (int64_t)((intptr_t)By->col(0) - (intptr_t)Bx->col(0));
+    if (d % stride != 0) return false;
+    *shift = d / stride;
+    return true;
+}
+// Column j of B as an index on the lattice base + i * ld * ed (see lk_context_s::memo): false when it does not lie on it.
+inline bool col_index(const double *base, int64_t ld, lk_basis_t B, int j, int64_t *i) {
+    const int64_t stride = ld * B->ed() * (int64_t)sizeof(double);
+    if (!base || B->ld != ld || stride < 1) return false;
+    const int64_t d = (int64_t)((intptr_t)B->col(j) - (intptr_t)base);
+    if (d % stride != 0) return false;
+    *i = d / stride;
+    return true;
 }
 
 int allreduce(lk_context_t c, double *dev, int64_t count) {
@@ -1158,7 +1215,7 @@ int fused_sub_with_dots(lk_context_t c) {
     LKCHK(fetch(c, 0, 1, red_stride(q.cnt)));
     auto &mm = c->memo;
     mm.vals.assign(c->red_host.get(), c->red_host + (size_t)q.cnt * ED);
-    mm.valid = true; mm.xbase = q.Bx->data; mm.y = y; mm.j0 = q.j0; mm.cnt = q.cnt;
+    mm.valid = true; mm.xbase = q.Bx->data; mm.xld = q.Bx->ld; mm.y = y; mm.j0 = q.j0; mm.cnt = q.cnt;
     c->nmemo.valid = true; c->nmemo.y = y; c->nmemo.nrm2 = c->red_host[(size_t)q.cnt * ED];
     c->fusion_stats[0] += 1;
     return LK_OK;
@@ -1939,6 +1996,9 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
     if (!alpha || !beta) return fail(LK_ERR_INVALID, "lk_vec_axpby: null scalar");
     lk_context_t c = Bx->ctx;
     const bool cp = Bx->dtype == LK_C128;
+    // x == y is the in-place update; a column shifted by a few rows is neither that nor a second vector
+    if (Bx->col(jx) != By->col(jy) && cols_overlap(Bx, jx, 1, By, jy, 1))
+        return fail(LK_ERR_INVALID, "lk_vec_axpby: the two columns overlap without being the same column");
     By->touch(jy);
     if (c->lazy) {
         const int ED = Bx->ed();
@@ -1966,8 +2026,10 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
         if (unit_beta && Bx->ncols > 1 && xp != yp && xp != T) {
             LKCHK(apply_sub(c));                                 // an earlier y update used the queue as it was
             const bool same_target = q.active && q.By && q.By->col(q.jy) == yp;
+            // the next column of the queue's panel, by address: whatever handle names it, as long as the queue's own handle holds it
+            int64_t inext = 0;
             const bool extends = same_target && q.cnt < KMAX_WIDE &&
-                                 (q.cnt == 0 || (q.Bx == Bx && jx == q.j0 + q.cnt));
+                                 (q.cnt == 0 || (col_index(q.Bx->data, q.Bx->ld, Bx, jx, &inext) && inext == q.j0 + q.cnt && inext < q.Bx->ncols));
             if (!extends) {
                 const VecRef w{By, jy}, r{Bx, jx};
                 LKCHK(lazy_enter_vec(c, &w, false, &r, &w));
@@ -1998,22 +2060,23 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
 static int speculative_first_pass(lk_context_t c, lk_basis_t B, int j, int *done) {
     *done = 0;
     auto &sp = c->spec;
-    if (!c->lazy || !c->lazy_speculate || !sp.armed || sp.xbase != B->data || j != sp.jy + 1) return LK_OK;
+    int64_t ij = 0;                                    // column j of B on the lattice the pattern was seen on (B may be another handle onto it)
+    if (!c->lazy || !c->lazy_speculate || !sp.armed || !col_index(sp.xbase, sp.xld, B, j, &ij) || ij != sp.jy + 1) return LK_OK;
     if (sp.unused) { sp.armed = false; c->spec_stats[1] += 1; return LK_OK; }      // the last prediction was wasted: stop predicting
-    const int cnt = j - sp.j0;
-    if (cnt < 2 || cnt > KMAX_WIDE || j >= B->ncols || B->hwm <= j || c->sub.active) return LK_OK;
+    const int cnt = (int)(ij - sp.j0), b0 = j - cnt;   // the swept columns in B's own numbering: [b0, j)
+    if (cnt < 2 || cnt > KMAX_WIDE || b0 < 0 || j >= B->ncols || B->hwm <= j || c->sub.active) return LK_OK;
     // (a virtual temporary elsewhere -- the previous step's last projection, never asked for -- does not matter; one INSIDE the
     //  swept columns does: its contents are not in memory)
-    if (c->queue.active && c->queue.By && c->queue.By->data == B->data && c->queue.jy >= sp.j0 && c->queue.jy <= j) return LK_OK;
+    if (c->queue.active && c->queue.By && cols_overlap(c->queue.By, c->queue.jy, 1, B, b0, cnt + 1)) return LK_OK;
     const int ED = B->ed();
     double *y = B->col(j);
-    LKCHK((sweepm<1>(B, sp.j0, cnt, y, nullptr, nullptr, 0, c->red)));
+    LKCHK((sweepm<1>(B, b0, cnt, y, nullptr, nullptr, 0, c->red)));
     LKCHK(fetch(c, 0, 1, red_stride(cnt)));
     auto &mm = c->memo;
     mm.vals.assign(c->red_host.get(), c->red_host + (size_t)cnt * ED);
-    mm.valid = true; mm.xbase = B->data; mm.y = y; mm.j0 = sp.j0; mm.cnt = cnt;
+    mm.valid = true; mm.xbase = B->data; mm.xld = B->ld; mm.y = y; mm.j0 = b0; mm.cnt = cnt;
     c->nmemo.valid = true; c->nmemo.y = y; c->nmemo.nrm2 = c->red_host[(size_t)cnt * ED];
-    sp.jy = j; sp.unused = true;
+    sp.jy = (int)ij; sp.unused = true;
     c->spec_stats[0] += 1;
     c->lazy_stats[1] += 1;
     *done = 1;
@@ -2029,8 +2092,9 @@ int lk_vec_dot(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out) {
     lk_context_t c = Bx->ctx;
     // y%norm() reaches the plugin as y%dot(y): LightKrylov's norm is sqrt(abs(self%dot(self))) (AbstractVectors.fypp:424-432)
     const bool self_dot = Bx->col(jx) == By->col(jy);
+    int64_t iq = 0;                                    // column jx of Bx among the queue's columns, whatever handle names it
     if (c->lazy && c->sub.active && c->sub.By->col(c->sub.jy) == By->col(jy) &&
-        (self_dot || (Bx->data == c->queue.Bx->data && jx >= c->queue.j0 && jx < c->queue.j0 + c->queue.cnt))) {
+        (self_dot || (col_index(c->queue.Bx->data, c->queue.Bx->ld, Bx, jx, &iq) && iq >= c->queue.j0 && iq < c->queue.j0 + c->queue.cnt))) {
         LKCHK(fused_sub_with_dots(c));                           // the norm / the first dot of the next pass: one fused sweep
     } else {
         const VecRef r1{Bx, jx}, r2{By, jy};
@@ -2050,20 +2114,27 @@ int lk_vec_dot(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out) {
         if (self_dot) c->spec.last_norm_y = By->col(jy);       // a plain norm: remember it (the dots that follow may complete the pattern)
         else if (c->spec.last_norm_y != By->col(jy)) c->spec.last_norm_y = nullptr;
     }
-    if (c->lazy && c->xhy_mfma && Bx->data == By->data && Bx->ncols > 1) {
+    // y as a column of Bx's own lattice (jyx, which may lie outside Bx): "the same panel" by address, so through a view too
+    int64_t jyx = 0;
+    const bool y_on_x = c->lazy && col_index(Bx->data, Bx->ld, By, jy, &jyx);
+    if (c->lazy && c->xhy_mfma && y_on_x && jyx >= 0 && jyx < Bx->ncols && Bx->ncols > 1) {
         // gram_matrix's loop: see gmemo
         auto &gm = c->gmemo;
         const int ED = Bx->ed();
+        int64_t gx = jx, gy = jyx;                     // the two columns on the memo's lattice
         auto serve = [&]() {
-            for (int e = 0; e < ED; ++e) out[e] = gm.G[((size_t)jy * gm.cnt + jx) * ED + e];
+            for (int e = 0; e < ED; ++e) out[e] = gm.G[((size_t)gy * gm.cnt + gx) * ED + e];
             c->lazy_stats[0] += 1;
         };
-        if (gm.valid && gm.xbase == Bx->data && jx < gm.cnt && jy < gm.cnt) { serve(); return LK_OK; }
-        const bool run = gm.last_x == Bx->data && gm.last_jx == jx && gm.last_jy + 1 == jy;
-        gm.last_x = Bx->data; gm.last_jx = jx; gm.last_jy = jy;
+        if (gm.valid && col_index(gm.xbase, gm.xld, Bx, jx, &gx) && col_index(gm.xbase, gm.xld, By, jy, &gy) && gx >= 0 && gx < gm.cnt &&
+            gy >= 0 && gy < gm.cnt) { serve(); return LK_OK; }
+        gx = jx; gy = jyx;
+        const double *xp = Bx->col(jx), *yq = By->col(jy);
+        const bool run = gm.last_x == xp && gm.last_y && gm.last_y + Bx->ld * ED == yq;
+        gm.last_x = xp; gm.last_y = yq;
         int cnt = Bx->hwm < Bx->ncols ? Bx->hwm : Bx->ncols;
         if (cnt > XHY_MAX) cnt = XHY_MAX;
-        if (run && !c->queue.active && !c->sub.active && cnt >= XHY_MIN_P && jx < cnt && jy < cnt) {
+        if (run && !c->queue.active && !c->sub.active && cnt >= XHY_MIN_P && jx < cnt && jyx < cnt) {
             double *dev = nullptr;
             LKCHK(dots_mfma(Bx, 0, cnt, Bx, 0, cnt, 1 | 2, 0, &dev));
             std::vector<double> host((size_t)cnt * (cnt + 1) * ED);
@@ -2080,7 +2151,7 @@ int lk_vec_dot(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out) {
                     }
             if (ED == 2)
                 for (int j = 0; j < cnt; ++j) gm.G[((size_t)j * cnt + j) * 2 + 1] = 0.0;   // x . x is real (dotc sums exact zeros)
-            gm.valid = true; gm.xbase = Bx->data; gm.cnt = cnt;
+            gm.valid = true; gm.xbase = Bx->data; gm.xld = Bx->ld; gm.cnt = cnt;
             c->lazy_stats[1] += 1;
             serve();
             return LK_OK;
@@ -2092,30 +2163,32 @@ int lk_vec_dot(lk_basis_t Bx, int jx, lk_basis_t By, int jy, double *out) {
         const int ED = Bx->ed();
         auto &mm = c->memo;
         const double *yp = By->col(jy);
-        if (mm.valid && mm.xbase == Bx->data && mm.y == yp && jx >= mm.j0 && jx < mm.j0 + mm.cnt) {
-            for (int e = 0; e < ED; ++e) out[e] = mm.vals[(size_t)(jx - mm.j0) * ED + e];
+        int64_t ix = 0, isy = 0;
+        if (mm.valid && mm.y == yp && col_index(mm.xbase, mm.xld, Bx, jx, &ix) && ix >= mm.j0 && ix < mm.j0 + mm.cnt) {
+            for (int e = 0; e < ED; ++e) out[e] = mm.vals[(size_t)(ix - mm.j0) * ED + e];
             c->lazy_stats[0] += 1;
-            if (c->spec.armed && c->spec.xbase == Bx->data && c->spec.jy == jy) c->spec.unused = false;   // the anticipated sweep was wanted
+            if (c->spec.armed && col_index(c->spec.xbase, c->spec.xld, By, jy, &isy) && isy == c->spec.jy) c->spec.unused = false;   // the anticipated sweep was wanted
             return LK_OK;
         }
         // X(:k) vs y = X(k+1) in the same panel; otherwise the run of columns ever written (slab panels are mostly
         // unused columns: sweeping them would cost up to 128/k times the eager traffic)
-        int jend = (By->data == Bx->data && jy > jx) ? jy : (Bx->hwm < Bx->ncols ? Bx->hwm : Bx->ncols);
+        int jend = (y_on_x && jyx > jx && jyx <= Bx->ncols) ? (int)jyx : (Bx->hwm < Bx->ncols ? Bx->hwm : Bx->ncols);
         int cnt = jend - jx;
         if (cnt > KMAX_WIDE) cnt = KMAX_WIDE;               // one (lane-split) sweep holds up to 512 columns
-        if (c->queue.active && c->queue.By && c->queue.By->data == Bx->data && c->queue.jy > jx && c->queue.jy < jx + cnt)
-            cnt = c->queue.jy - jx;                              // never sweep a column whose contents are still virtual
-        const bool y_inside = (By->data == Bx->data) && jy >= jx && jy < jx + cnt;
+        int64_t it = 0;
+        if (c->queue.active && c->queue.By && col_index(Bx->data, Bx->ld, c->queue.By, c->queue.jy, &it) && it > jx && it < jx + cnt)
+            cnt = (int)(it - jx);                                // never sweep a column whose contents are still virtual
+        const bool y_inside = y_on_x && jyx >= jx && jyx < jx + cnt;
         if (cnt >= 2 && !y_inside) {
             LKCHK((sweepm<1>(Bx, jx, cnt, By->col(jy), nullptr, nullptr, 0, c->red)));
             LKCHK(fetch(c, 0, 1, red_stride(cnt)));
             mm.vals.assign(c->red_host.get(), c->red_host + (size_t)cnt * ED);
-            mm.valid = true; mm.xbase = Bx->data; mm.y = yp; mm.j0 = jx; mm.cnt = cnt;
+            mm.valid = true; mm.xbase = Bx->data; mm.xld = Bx->ld; mm.y = yp; mm.j0 = jx; mm.cnt = cnt;
             c->lazy_stats[1] += 1;
             // norm of column jy, then the dots of ALL columns before it against it: the opening of a Gram-Schmidt pass against
             // X(:jy) with y = X(jy + 1) of the same panel.  The next step's norm may run this sweep at once (spec).
-            if (By->data == Bx->data && jx < jy && cnt == jy - jx && c->spec.last_norm_y == yp) {
-                c->spec.armed = true; c->spec.xbase = Bx->data; c->spec.jy = jy; c->spec.j0 = jx; c->spec.unused = false;
+            if (y_on_x && jx < jyx && cnt == jyx - jx && c->spec.last_norm_y == yp) {
+                c->spec.armed = true; c->spec.xbase = Bx->data; c->spec.xld = Bx->ld; c->spec.jy = (int)jyx; c->spec.j0 = jx; c->spec.unused = false;
             }
             for (int e = 0; e < ED; ++e) out[e] = mm.vals[e];
             return LK_OK;
@@ -2170,6 +2243,7 @@ int lk_vec_copy(lk_basis_t Bd, int jd, lk_basis_t Bs, int js) {
     DevGuard dev_guard(Bd->ctx);
     LKCHK(check_pair(Bd, Bs, "lk_vec_copy"));
     if (Bd->col(jd) == Bs->col(js)) return LK_OK;
+    if (cols_overlap(Bd, jd, 1, Bs, js, 1)) return fail(LK_ERR_INVALID, "lk_vec_copy: the two columns overlap without being the same column");
     {
         const VecRef w{Bd, jd}, r{Bs, js};
         LKCHK(lazy_enter_vec(Bd->ctx, &w, true, &r, nullptr));
@@ -2230,11 +2304,13 @@ static int innerprod_impl(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, d
     // X^H X entries on the diagonal, complex kind: conj(x) . x has an imaginary part of exactly zero in the reference's dotc (every term is
     // re*im - im*re, no contraction across the two products); the three-product matrix-core kernels form Im as P3 + P1 - P2, the doubled real
     // problem and the FMA-contracted vector kernels round one of the two products -- each leaves O(eps |x|^2) there.  Zeroed, whatever kernel ran.
+    int64_t yshift = 0;                                // column j of By is column j + yshift of Bx -- by address, so through a view too
+    const bool shared = same_columns(Bx, By, &yshift);
     auto real_diagonal = [&]() {
-        if (ED != 2 || Bx->data != By->data) return;
+        if (ED != 2 || !shared) return;
         for (int q = 0; q < p; ++q) {
-            const int i = jy0 + q;                     // column i of X is column q of Y
-            if (i < k) M[((size_t)q * k + i) * 2 + 1] = 0.0;
+            const int64_t i = yshift + jy0 + q;        // column i of X is column q of Y
+            if (i >= 0 && i < k) M[((size_t)q * k + i) * 2 + 1] = 0.0;
         }
     };
     if (c->xhy_mfma && p >= XHY_MIN_P) {
@@ -2244,7 +2320,7 @@ static int innerprod_impl(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, d
             const int pn = (p - j) < XHY_MAX ? (p - j) : XHY_MAX;
             for (int c0 = 0; c0 < k; c0 += XHY_MAX) {
                 const int kk = (k - c0) < XHY_MAX ? (k - c0) : XHY_MAX;
-                const bool same = Bx->data == By->data && jy0 + j == c0 && pn == kk;          // a diagonal block of X^H X
+                const bool same = shared && yshift + jy0 + j == c0 && pn == kk;          // a diagonal block of X^H X
                 double *out = nullptr;
                 LKCHK(dots_mfma(Bx, c0, kk, By, jy0 + j, pn, same ? (1 | (upper_only ? 2 : 0)) : 0, 0, &out));
                 HIPCHK(hipMemcpyAsync(host.data(), out, (size_t)pn * (kk + 1) * ED * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2308,12 +2384,12 @@ int lk_lincomb(lk_basis_t Bx, int k, const double *C, int q, lk_basis_t By, int 
     LKCHK(check_pair(Bx, By, "lk_lincomb"));
     if (k < 1 || k > Bx->ncols || q < 1 || jy0 < 0 || jy0 + q > By->ncols)
         return fail(LK_ERR_INVALID, "Krylov basis X and combination matrix B have incompatible sizes.");
+    // the output columns must not be among the inputs (the reference writes into a fresh Xwrk / proj) -- by address: see cols_overlap
+    if (cols_overlap(Bx, 0, k, By, jy0, q)) return fail(LK_ERR_INVALID, "lk_lincomb: output columns alias the input basis");
     lk_context_t c = Bx->ctx;
     LKCHK(lazy_enter(c, true));
     const int ED = Bx->ed();
     By->touch(jy0, q);
-    // the output columns must not be among the inputs (the reference writes into a fresh Xwrk / proj)
-    if (Bx->data == By->data && jy0 < k) return fail(LK_ERR_INVALID, "lk_lincomb: output columns alias the input basis");
     // coefficients: one upload of the whole k x q block, repacked on the device for the kernel's scalar loads
     const int64_t raw = (int64_t)k * q * ED;
     LKCHK(c->scratch.reserve(raw + gemm_packed_doubles(k, q, ED)));
@@ -2335,10 +2411,8 @@ static int dgs_generic(lk_basis_t Bx, int k, lk_basis_t By, int jy, double *h, d
     LKCHK(lazy_enter(c, true));
     const int ED = Bx->ed();
     double *y = By->col(jy);
-    {   // y must not lie inside the device range of X(:, :k) -- compared by address, so a wrapped view of the same panel counts
-        const double *x0 = Bx->col(0), *x1 = Bx->col(k - 1) + Bx->n * ED;
-        if (y + Bx->n * ED > x0 && y < x1) return fail(LK_ERR_INVALID, "double_gram_schmidt_step: y is one of the basis columns");
-    }
+    // y must not meet a column of X(:, :k) -- compared by address, so a wrapped view of the same panel counts (cols_overlap)
+    if (cols_overlap(Bx, 0, k, By, jy, 1)) return fail(LK_ERR_INVALID, "double_gram_schmidt_step: y is one of the basis columns");
     double n0 = 0, n1 = 0, n2 = 0;
     resident_maybe_rearm(c);
     bool single = two_pass && k <= KMAX_WIDE && resident_applies(Bx, k);
@@ -2480,7 +2554,7 @@ static int gemm_subtract(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int qn, c
 // then pass 2, pn * (kk + 1) * ED doubles each, slot kk of a column = ||Y_q||^2); `collect` reads a host copy of it.
 static bool dgs_block_fused_ok(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p) {
     return k >= 1 && k <= KMAX_WIDE && k <= Bx->ncols && p >= 2 && Bx->ctx == By->ctx && Bx->dtype == By->dtype && Bx->n == By->n &&
-           !(Bx->data == By->data && jy0 < k) && (k <= KMAX_FUSED || Bx->ctx->xhy_mfma);
+           !cols_overlap(Bx, 0, k, By, jy0, p) && (k <= KMAX_FUSED || Bx->ctx->xhy_mfma);
 }
 static bool dgs_block_on_mfma(lk_basis_t Bx, int k, int p) { return Bx->ctx->xhy_mfma && (p >= XHY_MIN_P || k > KMAX_FUSED); }
 static int64_t dgs_block_slot_doubles(lk_basis_t Bx, int k, int p) {
@@ -2620,6 +2694,9 @@ int lk_dgs_block(lk_basis_t Bx, int k, lk_basis_t By, int jy0, int p, double *h,
     if (p < 1 || jy0 < 0 || jy0 + p > By->ncols) return fail(LK_ERR_INVALID, "lk_dgs_block: bad column range");
     const int ED = Bx->ed();
     int inf = 0;
+    // no column of Y may meet X(:, :k): decided here, by address, before the route is chosen (the panel x panel schedule has no check of its own)
+    if (k >= 1 && k <= Bx->ncols && Bx->ctx == By->ctx && Bx->dtype == By->dtype && Bx->n == By->n && cols_overlap(Bx, 0, k, By, jy0, p))
+        return fail(LK_ERR_INVALID, "lk_dgs_block: a column of Y is one of the basis columns");
     if (dgs_block_fused_ok(Bx, k, By, jy0, p)) {
         // panel x panel schedule; ONE copy + synchronisation per call (round 6; one per group of columns before)
         lk_context_t c = Bx->ctx;
@@ -2987,7 +3064,7 @@ int lk_bidiag(lk_linop_t A, lk_basis_t U, lk_basis_t V, double *B, int64_t ldb, 
     if (kstart < 1 || kend > kdim || kstart > kend + 1) return fail(LK_ERR_INVALID, "lk_bidiag: bad kstart/kend %d..%d (kdim %d)", kstart, kend, kdim);
     if (!(tol >= ATOL_DP)) return fail(LK_ERR_INVALID, "lk_bidiag: tol below atol_dp is not fused (the device-side stop is at max(tol, atol_dp))");
     if (ldb < kdim + 1) return fail(LK_ERR_INVALID, "lk_bidiag: ldb too small");
-    if (U->data == V->data) return fail(LK_ERR_INVALID, "lk_bidiag: U and V must be different bases");
+    if (cols_overlap(U, 0, U->ncols, V, 0, V->ncols)) return fail(LK_ERR_INVALID, "lk_bidiag: U and V must be different bases");
     lk_context_t c = U->ctx;
     DevGuard dev_guard(c);
     const int ED = U->ed();
@@ -3561,10 +3638,11 @@ int kexpm_progress(void *user, int kfirst, int klast) {
     return 0;
 }
 
-// the device range [lo, hi) of columns [j0, j1) of a panel, rows [0, n)
+// the column at p (rows [0, n)) against columns [j0, j1) of a panel: the one rule, cols_overlap
 bool overlaps(const double *p, lk_basis_t B, int j0, int j1) {
-    const double *lo = B->col(j0), *hi = B->col(j1 - 1) + B->n * B->ed();
-    return p + B->n * B->ed() > lo && p < hi;
+    ColSet one = colset(B, j0, 1);
+    one.p = (intptr_t)p;
+    return cols_overlap(one, colset(B, j0, j1 - j0));
 }
 }  // namespace
 
@@ -3775,7 +3853,7 @@ int lk_linop_residual(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_basis_t
     LKCHK(check_pair(Bb, Br, "lk_linop_residual(b, r)"));
     lk_context_t c = Br->ctx;
     if (A->ctx != c || A->dtype != Br->dtype || A->n != Br->n) return fail(LK_ERR_INVALID, "lk_linop_residual: operator/vector mismatch");
-    if (Br->col(jr) == Bx->col(jx) || Br->col(jr) == Bb->col(jb)) return fail(LK_ERR_INVALID, "lk_linop_residual: r is the same column as x or b");
+    if (cols_overlap(Br, jr, 1, Bx, jx, 1) || cols_overlap(Br, jr, 1, Bb, jb, 1)) return fail(LK_ERR_INVALID, "lk_linop_residual: r is the same column as x or b");
     DevGuard dev_guard(c);
     LKCHK(lazy_enter(c, true));
     LKCHK(residual_device(A, trans, Bx, jx, Bb, jb, Br, jr, c->red));

@@ -691,7 +691,7 @@ int lk_linop_apply(lk_linop_t op, int trans, lk_basis_t Bx, int jx, lk_basis_t B
     lk_context_t c = op->ctx;
     const double *x = Bx->col(jx);
     double *y = By->col(jy);
-    if (x == y) return fail(LK_ERR_INVALID, "lk_linop_apply: vec_in and vec_out alias");
+    if (cols_overlap(Bx, jx, 1, By, jy, 1)) return fail(LK_ERR_INVALID, "lk_linop_apply: vec_in and vec_out alias");
     const VecRef w{By, jy}, r{Bx, jx};
     LKCHK(lazy_enter_vec(c, &w, true, &r, nullptr));           // vec_out is intent(out): AbstractLinops.fypp:74-87
     By->touch(jy);

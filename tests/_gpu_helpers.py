@@ -492,3 +492,125 @@ def arnoldi_block_step_longdouble(d, X, p):
         R[j, j] = np.sqrt((W[:, j].conj() @ W[:, j]).real)
         W[:, j] = W[:, j] / R[j, j]
     return Hb, R, W
+
+
+# ---- two routes to the same columns (tests/test_gpu_views.py) ---------------------------------------------------------------------------
+def dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def bits(a):
+    """the 64-bit words of an array, column by column"""
+    return np.ascontiguousarray(np.asarray(a).T).view(np.uint64)
+
+
+def last_error():
+    return _capi.load().lk_last_error().decode()
+
+
+class TwoRoutes:
+    """The same n x w contents A twice.  Route P: an engine-owned panel R of exactly w columns, every operand named as (R, column index).
+    Route V: columns [a, a + w) of a wider engine-owned parent, every operand named through an offset view of its own (`P.view`, i.e.
+    lk_basis_wrap at col(a + j0)): the handles differ, the memory is one panel.  Both parents come from lk_basis_create with the same n, so
+    ld and the alignment of every column agree.  `check` asserts that the two panels hold the same bits afterwards and that the columns
+    of the wide parent outside [a, a + w) are untouched; it returns the contents.  `split`: route P holds columns [0, split) and
+    [split, w) in two panels (an entry that takes its column count from the handle -- a workspace, U against V -- cannot share one handle
+    with its other operands); an operand then lies on one side of the split.
+
+    Route P's panel has its own address and its own ncols, so the comparison holds only where no kernel is chosen from either.  In eager
+    mode lk_engine.hip reads a handle's ncols for range checks, for kdim = ncols - 1 of lk_arnoldi / lk_lanczos / lk_bidiag / lk_kexpm
+    (`const int kdim = X->ncols - 1`: the same on both routes, the view is made that wide), for lk_arnoldi_block's kdim = (ncols - p) / p and
+    for the HOST leading dimension of lk_kexpm's projected matrix (`const int64_t ldh = X->ncols`); hwm is read by the lazy path only
+    (lk_vec_dot's batched sweeps, speculative_first_pass).  No kernel or grid is chosen from them, and the columns of both parents start
+    on the same 256-byte grid with the same ld."""
+
+    def __init__(self, ctx, A, a=3, tail=2, split=None):
+        A = np.asfortranarray(A)
+        n, w = A.shape
+        self.a, self.w = a, w
+        self.split = w if split is None else split
+        self.Rs = [lk.krylov_basis_gpu(n, c1 - c0, A.dtype, ctx) for c0, c1 in ((0, self.split), (self.split, w)) if c1 > c0]
+        for R, c0 in zip(self.Rs, (0, self.split)):
+            R.upload(A[:, c0:c0 + R.ncols])
+        self.R = self.Rs[0]
+        self.img = basis(n, a + w + tail, A.dtype, 7100)
+        self.img[:, a:a + w] = A
+        self.P = lk.krylov_basis_gpu(n, a + w + tail, A.dtype, ctx)
+        self.P.upload(self.img)
+        self._views = []
+
+    def p(self, j0, w):
+        assert j0 + w <= self.split or j0 >= self.split
+        return (self.Rs[0]._h, j0) if j0 < self.split else (self.Rs[1]._h, j0 - self.split)
+
+    def v(self, j0, w):
+        V = self.P.view(self.a + j0, w)
+        assert V._h.value != self.P._h.value
+        self._views.append(V)
+        return V._h, 0
+
+    def routes(self):
+        return (self.p, self.v)
+
+    def check(self, what):
+        r, g = np.asfortranarray(np.column_stack([R.download() for R in self.Rs])), self.P.download()
+        a, w = self.a, self.w
+        assert np.array_equal(bits(g[:, a:a + w]), bits(r)), f"{what}: the panel differs between the parent route and the view route"
+        out = np.r_[0:a, a + w:g.shape[1]]
+        assert np.array_equal(bits(g[:, out]), bits(self.img[:, out])), f"{what}: a column outside the views changed"
+        return r
+
+
+class InterleavedPair:
+    """Two n x ncols panels A and B in ONE flat buffer with ld = 2 n_pad: A in rows [0, n) of every column, B wrapped n_pad rows further
+    on, so each lives entirely in the other's padding rows (`together`), or the same two panels with the same ld and alignment in two
+    buffers of their own (`together = False`).  Every other word is POISON; `get` asserts it still is and returns (A, B)."""
+
+    def __init__(self, ctx, dtype, n, ncols, together):
+        dt = np.dtype(dtype)
+        es = dt.itemsize
+        self.n, self.ncols, self.npad = n, ncols, (n + 31) // 32 * 32
+        self.ld = 2 * self.npad
+        total = self.ld * ncols
+        self.bufs, self.h = [], []
+        lib = _capi.load()
+        for i in range(1 if together else 2):
+            img = np.empty(total, dtype=dt)
+            img.view(np.uint64)[:] = POISON
+            b = lk.krylov_basis_gpu(total, 1, dt, ctx)
+            b.upload(img.reshape(-1, 1))
+            self.bufs.append(b)
+        for i in range(2):
+            b = self.bufs[0 if together else i]
+            h = C.c_void_p()
+            _capi.check(lib.lk_basis_wrap(ctx._h, _capi.LK_C128 if dt.kind == "c" else _capi.LK_F64, n, ncols, self.ld,
+                                          C.c_void_p(b.info()[4] + i * self.npad * es), C.byref(h)))
+            self.h.append(lk.krylov_basis_gpu(n, ncols, dt, ctx, _handle=h, _owner=b))
+        self.A, self.B = self.h
+        self.together, self.dtype = together, dt
+
+    def _rows(self, i, j):
+        o = j * self.ld + i * self.npad
+        return slice(o, o + self.n)
+
+    def set(self, i, M, col0=0):
+        M = np.asarray(M, dtype=self.dtype).reshape(self.n, -1, order="F")
+        b = self.bufs[0 if self.together else i]
+        buf = b.download()[:, 0]
+        for j in range(M.shape[1]):
+            buf[self._rows(i, col0 + j)] = M[:, j]
+        b.upload(buf.reshape(-1, 1))
+
+    def get(self, what=""):
+        out = []
+        bufs = [b.download()[:, 0] for b in self.bufs]
+        live = [np.zeros(bufs[0].size, dtype=bool) for _ in bufs]
+        for i in range(2):
+            k = 0 if self.together else i
+            out.append(np.asfortranarray(np.stack([bufs[k][self._rows(i, j)] for j in range(self.ncols)], axis=1)))
+            for j in range(self.ncols):
+                live[k][self._rows(i, j)] = True
+        for buf, lv in zip(bufs, live):
+            bad = np.flatnonzero(buf[~lv].view(np.uint64) != POISON)
+            assert bad.size == 0, f"{what}: {bad.size} words outside both panels changed"
+        return out

@@ -16,20 +16,47 @@ pytestmark = pytest.mark.gpu
 NV = 12            # vectors 0..NV-1 are the columns of one panel, NV and NV+1 are stand-alone vectors
 
 
-def _vec(B, S, i):
-    return B[i] if i < NV else S[i - NV]
+def draw_handle(vrng, views, i):
+    """which handle names panel column i: -1 the parent, else the index of one of the `views` (col0, ncols) that hold it"""
+    held = [v for v, (a, w) in enumerate(views) if a <= i < a + w]
+    if held and vrng.random() < 0.6:
+        return held[int(vrng.integers(len(held)))]
+    return -1
 
 
-def _run(seed, dtype, lazy):
+def _run(seed, dtype, lazy, views=(), lk=lk):
+    """`lk`: the package, or a stand-in with the same calls and no device (tests/test_views_generator.py replays the sequences on it).
+    `views`: (col0, ncols) of offset views of the panel (tests/test_gpu_views.py).  Each time the sequence names panel column j it is
+    reached as B[j], or -- drawn from a generator of its own, so the sequence of calls is the same with and without views -- as column
+    j - col0 of one of the views that hold it.  The last two entries of the returned stats count the vector operands named and how many
+    of them went through a view."""
     rng = np.random.default_rng(seed)
+    vrng = np.random.default_rng(77_000 + seed)
     n = 1501
     cplx = np.dtype(dtype).kind == "c"
     c = lk.Context(device=0)
     c.set_tuning("lazy", 1 if lazy else 0)
     B = lk.krylov_basis_gpu(n, NV, dtype, c)
     S = [lk.dense_vector_gpu(n, dtype, c) for _ in range(2)]
+    W = [B.view(a, w) for a, w in views]
+    named = [0, 0]
+
+    def _vec(i):
+        named[0] += 1
+        if i >= NV:
+            return S[i - NV]
+        v = draw_handle(vrng, views, i)
+        if v < 0:
+            return B[i]
+        named[1] += 1
+        return W[v][i - views[v][0]]
+
+    class _Named:                           # B[j] in the sequences below: a column of the panel, through whichever handle is drawn
+        def __getitem__(self, j):
+            return B[j] if isinstance(j, slice) else _vec(j)
+    P = _Named()
     for i in range(NV + 2):
-        _vec(B, S, i).rand(False, seed=100 + i)
+        (B[i] if i < NV else S[i - NV]).rand(False, seed=100 + i)
     out = []
 
     def scalar():
@@ -42,9 +69,9 @@ def _run(seed, dtype, lazy):
         cnt = int(rng.integers(1, NV - j0 + 1))
         cols = [j for j in range(j0, j0 + cnt) if j != T]
         if rng.random() < 0.85:
-            _vec(B, S, T).zero()
+            _vec(T).zero()
         for j in cols:
-            _vec(B, S, T).axpby(scalar(), B[j], 1.0)
+            _vec(T).axpby(scalar(), P[j], 1.0)
         return T, cols
 
     for _step in range(120):
@@ -53,14 +80,14 @@ def _run(seed, dtype, lazy):
             T, cols = projection()
             y = int(rng.integers(0, NV + 2))
             if y != T:
-                _vec(B, S, y).axpby(-1.0 if rng.random() < 0.7 else scalar(), _vec(B, S, T), 1.0)
+                _vec(y).axpby(-1.0 if rng.random() < 0.7 else scalar(), _vec(T), 1.0)
                 k = rng.random()
                 if k < 0.5:
-                    out.append(_vec(B, S, y).norm())
+                    out.append(_vec(y).norm())
                     for j in cols[: int(rng.integers(0, len(cols) + 1))]:
-                        out.append(B[j].dot(_vec(B, S, y)))
+                        out.append(P[j].dot(_vec(y)))
                 elif k < 0.7:
-                    out.append(_vec(B, S, y).dot(_vec(B, S, y)))
+                    out.append(_vec(y).dot(_vec(y)))
         elif r < 0.36:                          # gram_matrix's loop over a sub-range (self fixed, vec running), cut by a write
             i0 = int(rng.integers(0, NV - 3))
             i1 = int(rng.integers(i0 + 2, NV))
@@ -68,38 +95,38 @@ def _run(seed, dtype, lazy):
             cnt = 0
             for i in range(i0, i1 + 1):
                 for j in range(i, i1 + 1):
-                    out.append(B[i].dot(B[j]))
+                    out.append(P[i].dot(P[j]))
                     cnt += 1
                     if cnt == cut:
-                        B[int(rng.integers(0, NV))].scal(scalar())
+                        P[int(rng.integers(0, NV))].scal(scalar())
         elif r < 0.40:
             a, b = rng.integers(0, NV + 2, 2)
-            out.append(_vec(B, S, int(a)).dot(_vec(B, S, int(b))))
+            out.append(_vec(int(a)).dot(_vec(int(b))))
         elif r < 0.47:
-            out.append(_vec(B, S, int(rng.integers(0, NV + 2))).norm())
+            out.append(_vec(int(rng.integers(0, NV + 2))).norm())
         elif r < 0.55:
-            _vec(B, S, int(rng.integers(0, NV + 2))).scal(scalar())
+            _vec(int(rng.integers(0, NV + 2))).scal(scalar())
         elif r < 0.65:
             a, b = rng.integers(0, NV + 2, 2)
             if a != b:
                 beta = [0.0, 1.0, scalar()][int(rng.integers(0, 3))]
-                _vec(B, S, int(b)).axpby(scalar(), _vec(B, S, int(a)), beta)
+                _vec(int(b)).axpby(scalar(), _vec(int(a)), beta)
         elif r < 0.72:
             a, b = rng.integers(0, NV + 2, 2)
             if a != b:
-                lk.copy(_vec(B, S, int(b)), _vec(B, S, int(a)))
+                lk.copy(_vec(int(b)), _vec(int(a)))
         elif r < 0.77:
-            _vec(B, S, int(rng.integers(0, NV + 2))).zero()
+            _vec(int(rng.integers(0, NV + 2))).zero()
         elif r < 0.81:
-            _vec(B, S, int(rng.integers(0, NV + 2))).rand(False, seed=int(rng.integers(1, 1000)))
+            _vec(int(rng.integers(0, NV + 2))).rand(False, seed=int(rng.integers(1, 1000)))
         elif r < 0.86:
-            v = _vec(B, S, int(rng.integers(0, NV + 2)))
+            v = _vec(int(rng.integers(0, NV + 2)))
             out.append(float(np.abs(v.to_array()).sum()))                                   # single-vector download
         elif r < 0.90:
-            v = _vec(B, S, int(rng.integers(0, NV + 2)))
+            v = _vec(int(rng.integers(0, NV + 2)))
             v.basis.upload(np.full((n, 1), scalar(), dtype=dtype), v.col)                   # single-vector upload
         elif r < 0.95:
-            v = _vec(B, S, int(rng.integers(0, NV + 2)))                                    # a user's kernel on the vector
+            v = _vec(int(rng.integers(0, NV + 2)))                                    # a user's kernel on the vector
             acc = ["r", "w", "rw"][int(rng.integers(0, 3))]
             with c.torch_stream():                                                          # ordered with the engine's stream
                 t = v.as_torch(acc)
@@ -111,11 +138,11 @@ def _run(seed, dtype, lazy):
                     t.mul_(0.5)
         else:
             k = int(rng.integers(1, NV))
-            M = lk.innerprod(B[:k], B[k])                                                   # a panel-level call flushes everything
+            M = lk.innerprod(B[:k], P[k])                                                   # a panel-level call flushes everything
             out.extend(np.atleast_1d(M).tolist())
     final = [B.download()] + [s.to_array() for s in S]
-    stats = c.lazy_fusion_stats() + c.lazy_stats()
-    del B, S
+    stats = list(c.lazy_fusion_stats()) + list(c.lazy_stats()) + named
+    del B, S, W, P
     c.close()
     return out, final, stats
 
