@@ -63,6 +63,7 @@ module lightkrylov_gpu
     public :: gpu_kexpm_rdp, gpu_kexpm_cdp
     public :: gpu_qr_pivot_rdp, gpu_qr_pivot_cdp, gpu_kexpm_block_rdp, gpu_kexpm_block_cdp
     public :: gpu_gmres_rdp, gpu_gmres_cdp, gpu_linop_compose, gpu_residual_rdp, gpu_residual_cdp
+    public :: gpu_cg_rdp, gpu_cg_cdp
 
     type(c_ptr), save :: ctx = c_null_ptr
     integer(c_int64_t), save :: part_row0 = 0          ! first global row of this rank's block (lk_gpu_set_partition)
@@ -1163,5 +1164,50 @@ contains
         real(dp), optional, intent(out) :: res(:)
         integer, optional, intent(out) :: nres, n_inner, n_outer
         call gpu_gmres_rdp(op, Bb, jb, Bx, jx, V, info, rtol, atol, precond, kdim, maxiter, trans, res, nres, n_inner, n_outer)
+    end subroutine
+
+    !> cg (src/IterativeSolvers/CG/CG.fypp:60-196) as ONE engine call (lk_cg): solves A x = b, A symmetric / Hermitian positive definite,
+    !> for column jx (0-based) of the panel Bx (initial guess, overwritten) with b = column jb of Bb.  W: the caller's workspace panel of
+    !> at least 3 columns, 4 with a preconditioner.  precond: a fixed preconditioner given as an engine operator (z = M r, e.g. a diagonal
+    !> operator holding 1 / diag(A)); absent = none.  rtol, atol and maxiter default to the reference's (rtol_dp, atol_dp, 100).
+    !> info = +n_iter converged, -n_iter not; info = 0 (nres = 1, res(1) = 0, x as it came): the start residual is exactly zero
+    !> (CG.fypp:127 divides by it).  res (optional) receives the residual history up to its size, nres its full length.
+    subroutine gpu_cg_rdp(op, Bb, jb, Bx, jx, W, info, rtol, atol, precond, maxiter, res, nres)
+        type(c_ptr), intent(in) :: op, Bb, Bx, W
+        integer, intent(in) :: jb, jx
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: rtol, atol
+        type(c_ptr), optional, intent(in) :: precond
+        integer, optional, intent(in) :: maxiter
+        real(dp), optional, intent(out) :: res(:)
+        integer, optional, intent(out) :: nres
+        integer(c_int) :: cinfo, mi
+        integer(c_int64_t) :: nr
+        real(c_double) :: rt, at
+        real(c_double) :: none(1)
+        type(c_ptr) :: M
+        mi = 100; if (present(maxiter)) mi = maxiter                          ! cg_dp_opts, IterativeSolvers.fypp
+        at = 10.0_dp**(-precision(1.0_dp)); if (present(atol)) at = atol      ! atol_dp, Constants.f90:35
+        rt = sqrt(10.0_dp**(-precision(1.0_dp))); if (present(rtol)) rt = rtol   ! rtol_dp = sqrt(atol_dp), Constants.f90:37
+        M = c_null_ptr; if (present(precond)) M = precond
+        if (present(res)) then
+            call chk(lk_cg(op, M, Bb, int(jb, c_int), Bx, int(jx, c_int), W, rt, at, mi, res, int(size(res), c_int64_t), nr, cinfo), 'gpu_cg')
+        else
+            call chk(lk_cg(op, M, Bb, int(jb, c_int), Bx, int(jx, c_int), W, rt, at, mi, none, 0_c_int64_t, nr, cinfo), 'gpu_cg')
+        end if
+        info = cinfo
+        if (present(nres)) nres = int(nr)
+    end subroutine
+
+    subroutine gpu_cg_cdp(op, Bb, jb, Bx, jx, W, info, rtol, atol, precond, maxiter, res, nres)
+        type(c_ptr), intent(in) :: op, Bb, Bx, W
+        integer, intent(in) :: jb, jx
+        integer, intent(out) :: info
+        real(dp), optional, intent(in) :: rtol, atol
+        type(c_ptr), optional, intent(in) :: precond
+        integer, optional, intent(in) :: maxiter
+        real(dp), optional, intent(out) :: res(:)
+        integer, optional, intent(out) :: nres
+        call gpu_cg_rdp(op, Bb, jb, Bx, jx, W, info, rtol, atol, precond, maxiter, res, nres)
     end subroutine
 end module lightkrylov_gpu

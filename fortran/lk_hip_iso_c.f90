@@ -575,6 +575,22 @@ module lightkrylov_hip_c
             integer(c_int), intent(out) :: n_inner, n_outer, info
             integer(c_int) :: rc
         end function
+        !> conjugate gradient as one call (CG.fypp:60-196): A x = b, A symmetric / Hermitian positive definite, x = column jx of Bx
+        !> (initial guess, overwritten), b = column jb of Bb; M = c_null_ptr or a fixed preconditioner (an engine operator, z = M r);
+        !> W = workspace of >= 3 columns (4 with M).  res: res_cap entries of the residual history at most, nres its full length.
+        !> info = +n_iter converged, -n_iter not, 0 with nres = 1 and res(1) = 0 when the start residual is exactly zero: x is left as
+        !> it came (the reference returns NaN)
+        function lk_cg(A, M, Bb, jb, Bx, jx, W, rtol, atol, maxiter, res, res_cap, nres, info) bind(C, name="lk_cg") result(rc)
+            import :: c_int, c_ptr, c_double, c_int64_t
+            type(c_ptr), value :: A, M, Bb, Bx, W
+            integer(c_int), value :: jb, jx, maxiter
+            real(c_double), value :: rtol, atol
+            real(c_double), intent(inout) :: res(*)
+            integer(c_int64_t), value :: res_cap
+            integer(c_int64_t), intent(out) :: nres
+            integer(c_int), intent(out) :: info
+            integer(c_int) :: rc
+        end function
     end interface
 
 contains

@@ -607,6 +607,48 @@ int lk_kexpm_block(lk_linop_t A, int trans, lk_basis_t Bb, int jb0, lk_basis_t B
 int lk_gmres(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t V, double rtol, double atol,
              int kdim, int maxiter, double *res, int64_t res_cap, int64_t *nres, int *n_inner, int *n_outer, int *info);
 
+/* ---- conjugate gradient as one call --------------------------------------------------------------------------------------
+ * cg(A, b, x, info, rtol, atol, preconditioner, options, meta): src/IterativeSolvers/CG/CG.fypp:60-196.
+ * Solves A x = b for a symmetric / Hermitian positive definite A, applied as LK_OP_N only (cg has no transpose argument); x = column jx
+ * of Bx is the initial guess and is overwritten, b = column jb of Bb is read only.  M: NULL, or a FIXED preconditioner given as an
+ * engine operator, z = M r (:113, :134).  W: workspace of the CALLER, as in lk_gmres and lk_kexpm: >= 3 columns (r, p, Ap in columns
+ * 0, 1, 2), >= 4 with M (z in column 3), same context, kind and n_local.  No device memory is allocated beyond the context's grow-once
+ * workspaces (the iteration's scalars and the history ring are one of them).  options%maxiter is the argument of that name.
+ * What it computes.  tol = atol + rtol ||b|| (:87).  r = b - A x, the product only when ||x|| > 0 (:108-109); z = M r, p = z,
+ * rho = r.z, or p = r, rho = r.r (:113-116); res[0] = sqrt|rho| (:119).  Iteration i = 1..maxiter (:123): Ap = A p (:125);
+ * alpha = rho / (p.Ap) (:127); x += alpha p (:129); r -= alpha Ap (:131); z = M r and rho' = r.z, or rho' = r.r (:134-137); the residual
+ * sqrt|rho'| -- rho is complex for the complex kind (:141-145) -- joins the history (:148-149); residual < tol ends the loop converged,
+ * BEFORE the direction update (:151-154); else beta = rho' / rho (:157), p = (z or r) + beta p (:160-164), rho <- rho' (:167).
+ * info = +n_iter when converged, -n_iter otherwise (:175-179); maxiter = 0 gives nres = 1, info = 0.  A start residual below tol that
+ * is not zero still takes one iteration, as there.  res (may be NULL) receives at most res_cap entries of the history, nres (may be
+ * NULL) its full length, at most maxiter + 1.
+ * Schedule.  ONE host synchronisation at entry (||b|| and ||x||), then one PER DELIVERY and none per iteration.  The start residual is
+ * lk_linop_residual's, its sum left on the device (x = 0: a copy of b and its dot).  Per iteration, on the context's stream: the
+ * operator's kernels; p.Ap by the dot kernel and the engine's fixed-order reduce step; ONE launch that forms alpha on the device and
+ * updates x and r in one pass (four reads, two writes; the reference's two axpbys and the norm read take seven), leaving the per-block
+ * sums of r.r; with M the operator's kernels for z and the dot kernel for r.z; ONE one-block launch that finishes rho' in fixed order,
+ * writes it to the iteration's history slot, forms beta, raises the device stop flag at sqrt|rho'| < tol and rotates rho; ONE launch
+ * for p = z + beta p, beta read on the device.  The three are passes that run inside k_axpby's symbol, which adds no kernel instance.
+ * No floating-point atomics, nothing persistent, nothing that waits inside a launch.
+ * Complex quotients are (a + ib) / (c + id) = ((a + b t) / s, (b - a t) / s), t = d / c, s = c + d t for |c| >= |d|, and
+ * ((a t + b) / s, (b t - a) / s), t = c / d, s = c t + d otherwise, written out in the kernel.
+ * The host enqueues iterations at most 24 ahead of the last one whose history entry it has read (the look-ahead of
+ * lk_arnoldi_segments); history slots and the stop flag come back through pinned memory behind an event every 8 iterations and behind
+ * the last.  Every kernel of the batch carries the batch's guard; the direction update carries the number of the iteration it OPENS,
+ * so after a stop in iteration i nothing of iteration i + 1 runs: x is exactly the reference's x at exit, and columns 0 and 1 of W
+ * hold the r and p the reference leaves the loop with.  The launches enqueued past a stop are no-ops: at most 24 iterations' worth.
+ * Defined where the reference is not.  A START RESIDUAL OF EXACTLY ZERO (x the exact solution already, or b = 0 with x = 0): the
+ * reference computes 0 / 0 at :127 and returns NaN.  Here the call returns LK_OK with x unchanged, info = 0, nres = 1 and res[0] = 0,
+ * as lk_gmres does; the columns of W may be written.  A rho or p.Ap that is not finite, or p.Ap = 0 (A not definite): LK_ERR_NAN; the
+ * iteration that meets such a p.Ap writes nothing.  ||b|| or ||x|| not finite: LK_ERR_NAN before anything is written.
+ * LK_ERR_INVALID, with nothing written: a null A, W or info; maxiter < 0; the workspace too narrow; x or b overlapping one of the
+ * columns of W the call writes ([0, 3), [0, 4) with M); x and b overlapping; operator, preconditioner and vectors of different shape,
+ * kind or context; a ROW-SHARDED context (nranks > 1).
+ * Not provided: row-sharded contexts; a preconditioner that varies per iteration (it needs a host callback per iteration); the product
+ * fused into the update for row-local operators (what "fuse_rowop" does for the Arnoldi sweeps). */
+int lk_cg(lk_linop_t A, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t W, double rtol, double atol, int maxiter,
+          double *res, int64_t res_cap, int64_t *nres, int *info);
+
 #ifdef __cplusplus
 }
 #endif

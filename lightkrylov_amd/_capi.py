@@ -111,6 +111,7 @@ SIGNATURES = {
     "lk_linop_residual": (_int, [_p, _int, _p, _int, _p, _int, _p, _int, _dp]),
     "lk_gmres": (_int, [_p, _int, _p, _p, _int, _p, _int, _p, C.c_double, C.c_double, _int, _int, _dp, _i64, C.POINTER(_i64), _ip, _ip,
                         _ip]),
+    "lk_cg": (_int, [_p, _p, _p, _int, _p, _int, _p, C.c_double, C.c_double, _int, _dp, _i64, C.POINTER(_i64), _ip]),
 }
 
 

@@ -238,6 +238,8 @@ struct lk_context_s {
     int guard_step = 0;
     DevBuf<double> step_red;               // device: nsteps x RED_SECTIONS x RED_SECTION doubles
     PinnedBuf<double> step_red_host;       // pinned mirror
+    DevBuf<double> cg_state;               // lk_cg: the iteration's scalars (rho | p.Ap | beta | rho_0) and the history ring behind them
+    PinnedBuf<double> cg_host;             // pinned mirror
     int async_arnoldi = 1;                 // tuning key: 0 = one host round trip per step (the round-1 schedule)
     Guard guard() const { return Guard{guard_on ? stop_dev : nullptr, guard_step}; }
     // column pool (lk_pool_*): slabs handed out to per-object hosts
@@ -1148,7 +1150,7 @@ int materialise_queue(lk_context_t c) {
         ProfScope ps(c, "blas1", (double)q.Bx->n * q.Bx->ed() * 24.0);
         const auto kern = cp ? k_axpby<true> : k_axpby<false>;
         hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, q.coef[0], cp ? q.coef[1] : 0.0, q.Bx->col(q.j0), b, 0.0, T, q.Bx->n,
-                           blas1_nt(q.Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0);
+                           blas1_nt(q.Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0, CgArgs{});
         HIPCHK(hipGetLastError());
         return LK_OK;
     }
@@ -2051,7 +2053,7 @@ int lk_vec_axpby(const double *alpha, lk_basis_t Bx, int jx, const double *beta,
     ProfScope ps(c, "blas1", (double)Bx->n * Bx->ed() * 24.0);
     const auto kern = cp ? k_axpby<true> : k_axpby<false>;
     hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, alpha[0], cp ? alpha[1] : 0.0, Bx->col(jx), beta[0], cp ? beta[1] : 0.0,
-                       By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0);
+                       By->col(jy), Bx->n, blas1_nt(Bx), (const double *)nullptr, (double *)nullptr, (int64_t)0, CgArgs{});
     HIPCHK(hipGetLastError());
     return LK_OK;
 }
@@ -3679,7 +3681,7 @@ int lk_kexpm(lk_linop_t A, int trans, lk_basis_t Bb, int jb, lk_basis_t Bc, int 
         ProfScope ps(c, "blas1", (double)X->n * ED * 16.0);
         const auto kern = ED == 2 ? k_axpby<true> : k_axpby<false>;
         hipLaunchKernelGGL(kern, dim3(blas1_grid(c, nv)), dim3(256), 0, c->stream, 1.0, 0.0, b, 0.0, 0.0, X->col(0), X->n, blas1_nt(X), (const double *)c->red,
-                           (double *)nullptr, (int64_t)0);
+                           (double *)nullptr, (int64_t)0, CgArgs{});
         HIPCHK(hipGetLastError());
     }
 
@@ -3838,7 +3840,7 @@ static int residual_device(lk_linop_t A, int trans, lk_basis_t Bx, int jx, lk_ba
         ProfScope ps(c, "blas1", (double)Br->n * Br->ed() * 24.0);
         const auto kern = Br->dtype == LK_C128 ? k_axpby<true> : k_axpby<false>;     // its residual branch: the scalars are not read
         hipLaunchKernelGGL(kern, dim3(g), dim3(256), 0, c->stream, 0.0, 0.0, (const double *)Bb->col(jb), 0.0, 0.0, Br->col(jr), Br->n, blas1_nt(Br),
-                           (const double *)nullptr, (double *)c->partial, (int64_t)MAX_GRID);
+                           (const double *)nullptr, (double *)c->partial, (int64_t)MAX_GRID, CgArgs{});
     }
     HIPCHK(hipGetLastError());
     return reduce_partials(c, 0, 2, g, out_dev);
@@ -4103,6 +4105,190 @@ int lk_gmres(lk_linop_t A, int trans, lk_linop_t M, lk_basis_t Bb, int jb, lk_ba
         return gmres_impl(A, trans, M, Bb, jb, Bx, jx, V, bnorm, xnorm, rtol, atol, kdim, maxiter, res, res_cap, nres, n_inner, n_outer, info);
     } catch (const std::bad_alloc &) {
         return fail(LK_ERR_NOMEM, "lk_gmres: no host memory for the projected problem of %d columns", kdim);
+    }
+}
+
+// ---- conjugate gradient as one call ------------------------------------------------------------------------------------------------------
+// c->cg_state: CG_SC doubles of scalars -- rho (2) | p.Ap (2) | beta (2) | spare (2) -- and behind them a ring of CG_RING history slots
+// of CG_SLOT doubles, rho' (2) | p.Ap (2); iteration i (from 1) uses slot (i - 1) mod CG_RING.  c->cg_host mirrors it; its first two
+// doubles receive rho_0.  A delivery closes behind every CG_DELIVERY-th iteration and behind the last one: its slots and the stop flag
+// travel to the pinned mirror behind an event.  The ring is two look-ahead depths long and a whole number of deliveries, so a delivery's
+// slots are contiguous and none is written again before the host has read it.
+constexpr int CG_SC = 8, CG_SLOT = 4;
+constexpr int CG_DELIVERY = SEG_LOOKAHEAD / 3;
+constexpr int CG_RING = 2 * SEG_LOOKAHEAD;
+constexpr int CG_EVENTS = SEG_LOOKAHEAD / CG_DELIVERY + 1;   // deliveries in flight: at most SEG_LOOKAHEAD / CG_DELIVERY
+static_assert(CG_RING % CG_DELIVERY == 0 && SEG_LOOKAHEAD % CG_DELIVERY == 0, "a delivery's slots are contiguous in the ring");
+enum { CG_R = 0, CG_P = 1, CG_AP = 2, CG_Z = 3 };             // columns of the workspace
+
+// iteration `it` of CG.fypp:123-171 on the stream: everything of it under step `it`, the direction update under `it + 1`
+static int cg_enqueue(lk_linop_t A, lk_linop_t M, lk_basis_t Bx, int jx, lk_basis_t W, int it, double tol, BatchScope &batch) {
+    lk_context_t c = W->ctx;
+    const int ED = W->ed(), nt = blas1_nt(W);
+    const bool cp = W->dtype == LK_C128;
+    const int64_t nv = W->n * ED / 2 + 1;
+    const double colbytes = (double)W->n * ED * 8.0;
+    double *sc = c->cg_state, *hist = sc + CG_SC + (size_t)((it - 1) % CG_RING) * CG_SLOT;
+    batch.at(it);
+    LKCHK(lk_linop_apply(A, LK_OP_N, W, CG_P, W, CG_AP));                                        // :125
+    LKCHK(dot_device(W, CG_P, W, CG_AP, sc + 2));                                                 // :127, p.Ap
+    const int g = blas1_grid(c, nv, MAX_GRID);   // one partial per block: within the partial buffer's stride
+    // the three passes of lk_kernels.hip.h's conjugate-gradient section run inside k_axpby's symbol: its last argument names the pass
+    const auto kern = cp ? k_axpby<true> : k_axpby<false>;
+    auto pass = [&](int grid, double bytes, double *partial, const CgArgs &cg) -> int {
+        ProfScope ps(c, "blas1", bytes);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, c->stream, 0.0, 0.0, (const double *)nullptr, 0.0, 0.0, (double *)nullptr, W->n, nt,
+                           (const double *)nullptr, partial, (int64_t)MAX_GRID, cg);
+        HIPCHK(hipGetLastError());
+        return LK_OK;
+    };
+    CgArgs cg;
+    cg.sc = sc; cg.guard = c->guard();
+    cg.pass = CG_PASS_UPDATE; cg.a = W->col(CG_P); cg.b = W->col(CG_AP); cg.x = Bx->col(jx); cg.r = W->col(CG_R);
+    LKCHK(pass(g, colbytes * 6.0, M ? (double *)nullptr : (double *)c->partial, cg));               // :127-131, :137
+    if (M) {
+        LKCHK(lk_linop_apply(M, LK_OP_N, W, CG_R, W, CG_Z));                                      // :134
+        ProfScope ps(c, "blas1", colbytes * 2.0);
+        hipLaunchKernelGGL(cp ? k_dot<true> : k_dot<false>, dim3(g), dim3(256), 0, c->stream, (const double *)W->col(CG_R), (const double *)W->col(CG_Z), W->n,
+                           (double *)c->partial, (int64_t)MAX_GRID, nt);
+        HIPCHK(hipGetLastError());
+    }
+    cg = CgArgs{};
+    cg.sc = sc; cg.guard = c->guard();
+    cg.pass = CG_PASS_SCALARS; cg.hist = hist; cg.tol = tol; cg.stop_out = c->stop_dev; cg.nblocks = g;
+    LKCHK(pass(1, 0.0, (double *)c->partial, cg));                                                // :141-157, :167
+    batch.at(it + 1);
+    cg = CgArgs{};
+    cg.sc = sc; cg.guard = c->guard();
+    cg.pass = CG_PASS_DIRECTION; cg.a = W->col(M ? CG_Z : CG_R); cg.x = W->col(CG_P);
+    LKCHK(pass(blas1_grid(c, nv), colbytes * 3.0, (double *)nullptr, cg));                        // :160-164
+    return LK_OK;
+}
+
+static int cg_impl(lk_linop_t A, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t W, double tol, double xnorm, int maxiter,
+                   std::vector<double> &hist_out, int *info) {
+    lk_context_t c = W->ctx;
+    const bool cp = W->dtype == LK_C128;
+    LKCHK(c->cg_state.reserve(CG_SC + (int64_t)CG_RING * CG_SLOT));
+    LKCHK(c->cg_host.reserve(CG_SC + (int64_t)CG_RING * CG_SLOT));
+    LKCHK(c->seg_stop_host.reserve(CG_EVENTS));
+    while ((int)c->seg_events.size() < CG_EVENTS) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->seg_events.push_back(e);
+    }
+    double *sc = c->cg_state;
+    const double *hh = c->cg_host;
+    W->touch(0, M ? 4 : 3);
+    // r = b - A x, the product only for x != 0 (:108-109); rho_0 = r.r stays on the device
+    if (xnorm > 0.0) {
+        LKCHK(residual_device(A, LK_OP_N, Bx, jx, Bb, jb, W, CG_R, sc));
+    } else {
+        LKCHK(lk_vec_copy(W, CG_R, Bb, jb));
+        LKCHK(dot_device(W, CG_R, W, CG_R, sc));
+    }
+    if (M) {                                                                                      // :113-114
+        LKCHK(lk_linop_apply(M, LK_OP_N, W, CG_R, W, CG_Z));
+        LKCHK(lk_vec_copy(W, CG_P, W, CG_Z));
+        LKCHK(dot_device(W, CG_R, W, CG_Z, sc));
+    } else {
+        LKCHK(lk_vec_copy(W, CG_P, W, CG_R));                                                     // :116
+    }
+    HIPCHK(hipMemcpyAsync(c->cg_host, c->cg_state, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // rho_0, read at the first delivery
+    auto residual = [&](const double *rho) { return std::sqrt(cp ? std::hypot(rho[0], rho[1]) : std::fabs(rho[0])); };   // :141-145
+
+    BatchScope batch(c, false);
+    LKCHK(batch.begin());
+    int enq = 0, read = 0, nd_enq = 0, nd_read = 0;     // iterations enqueued / read by the host, deliveries closed / read
+    int stop_it = 0;
+    bool have_r0 = false;
+    *info = 0;
+    while (read < maxiter && !stop_it) {
+        // at most SEG_LOOKAHEAD iterations ahead of the last one whose history entry the host has read
+        const int ahead = read + SEG_LOOKAHEAD < maxiter ? read + SEG_LOOKAHEAD : maxiter;
+        for (; enq < ahead; ) {
+            ++enq;
+            LKCHK(cg_enqueue(A, M, Bx, jx, W, enq, tol, batch));
+            if (enq % CG_DELIVERY == 0 || enq == maxiter) {
+                const int first = (enq - 1) / CG_DELIVERY * CG_DELIVERY + 1, ev = nd_enq % CG_EVENTS;
+                const size_t off = CG_SC + (size_t)((first - 1) % CG_RING) * CG_SLOT;
+                HIPCHK(hipMemcpyAsync(c->cg_host + off, c->cg_state + off, (size_t)(enq - first + 1) * CG_SLOT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(c->seg_stop_host + ev, c->stop_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipEventRecord(c->seg_events[ev], c->stream));
+                ++nd_enq;
+            }
+        }
+        // the next delivery: ONE synchronisation for its iterations
+        const int ev = nd_read % CG_EVENTS;
+        HIPCHK(hipEventSynchronize(c->seg_events[ev]));
+        ++nd_read;
+        const int last = read + CG_DELIVERY < maxiter ? (read / CG_DELIVERY + 1) * CG_DELIVERY : maxiter;
+        const int flag = c->seg_stop_host[ev];
+        if (!have_r0) {
+            have_r0 = true;
+            if (!std::isfinite(hh[0]) || !std::isfinite(hh[1])) return fail(LK_ERR_NAN, "lk_cg: the start residual is not finite");
+            hist_out.push_back(residual(hh));                                                     // :119
+            if (hh[0] == 0.0 && hh[1] == 0.0) break;     // zero start residual: iteration 1 found p.Ap = 0 and wrote nothing; info = 0
+        }
+        for (int it = read + 1; it <= last && !stop_it; ++it) {
+            const double *s = hh + CG_SC + (size_t)((it - 1) % CG_RING) * CG_SLOT;
+            if (flag == it) {
+                stop_it = it;
+                if (!std::isfinite(s[2]) || !std::isfinite(s[3]) || (s[2] == 0.0 && s[3] == 0.0))
+                    return fail(LK_ERR_NAN, "lk_cg: p.Ap is zero or not finite in iteration %d", it);
+                if (!std::isfinite(s[0]) || !std::isfinite(s[1])) return fail(LK_ERR_NAN, "lk_cg: the residual of iteration %d is not finite", it);
+            }
+            hist_out.push_back(residual(s));                                                      // :148-149
+            *info = flag == it ? it : -it;                                                        // :151-154, :175-179
+        }
+        read = last;
+    }
+    if (maxiter == 0) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!std::isfinite(hh[0]) || !std::isfinite(hh[1])) return fail(LK_ERR_NAN, "lk_cg: the start residual is not finite");
+        hist_out.push_back(residual(hh));
+    }
+    int stop = 0;
+    return batch.finish(&stop);       // the look-ahead launches behind a stop (no-ops by the guard) have drained; the profiling records
+}
+
+int lk_cg(lk_linop_t A, lk_linop_t M, lk_basis_t Bb, int jb, lk_basis_t Bx, int jx, lk_basis_t W, double rtol, double atol, int maxiter,
+          double *res, int64_t res_cap, int64_t *nres, int *info) {
+    if (!A || !W || !info) return fail(LK_ERR_INVALID, "lk_cg: null argument");
+    LKCHK(check_vec(Bb, jb, "lk_cg(b)"));
+    LKCHK(check_vec(Bx, jx, "lk_cg(x)"));
+    LKCHK(check_pair(Bb, W, "lk_cg(b, W)"));
+    LKCHK(check_pair(Bx, W, "lk_cg(x, W)"));
+    lk_context_t c = W->ctx;
+    if (A->ctx != c || A->dtype != W->dtype || A->n != W->n) return fail(LK_ERR_INVALID, "lk_cg: operator/vector mismatch");
+    if (M && (M->ctx != c || M->dtype != W->dtype || M->n != W->n)) return fail(LK_ERR_INVALID, "lk_cg: preconditioner/vector mismatch");
+    if (c->nranks > 1) return fail(LK_ERR_INVALID, "lk_cg: row-sharded contexts (nranks = %d) are not supported", c->nranks);
+    if (maxiter < 0) return fail(LK_ERR_INVALID, "lk_cg: maxiter = %d", maxiter);
+    const int ncw = M ? 4 : 3;                                   // columns of W the call writes: r, p, Ap and, with M, z
+    if (W->ncols < ncw) return fail(LK_ERR_INVALID, "lk_cg: the workspace has %d columns, the call needs %d%s", W->ncols, ncw, M ? " with a preconditioner" : "");
+    if (res && res_cap < 0) return fail(LK_ERR_INVALID, "lk_cg: res_cap = %lld", (long long)res_cap);
+    if (cols_overlap(Bx, jx, 1, Bb, jb, 1)) return fail(LK_ERR_INVALID, "lk_cg: x and b overlap");
+    if (cols_overlap(Bx, jx, 1, W, 0, ncw)) return fail(LK_ERR_INVALID, "lk_cg: x overlaps a workspace column the call writes");
+    if (cols_overlap(Bb, jb, 1, W, 0, ncw)) return fail(LK_ERR_INVALID, "lk_cg: b overlaps a workspace column the call writes");
+    DevGuard dev_guard(c);
+    LKCHK(lazy_enter(c, true));
+    // the one synchronisation outside the deliveries: ||b|| for the tolerance (:87) and ||x|| for the test at :108
+    LKCHK(dot_device(Bb, jb, Bb, jb, c->red));
+    LKCHK(dot_device(Bx, jx, Bx, jx, c->red + RED_SECTION));
+    LKCHK(fetch(c, 0, 2));
+    const double bnorm = std::sqrt(std::fabs(c->red_host[0])), xnorm = std::sqrt(std::fabs(c->red_host[RED_SECTION]));
+    if (!std::isfinite(bnorm)) return fail(LK_ERR_NAN, "lk_cg: |b| is not finite");
+    if (!std::isfinite(xnorm)) return fail(LK_ERR_NAN, "lk_cg: |x| is not finite");
+    const double tol = atol + rtol * bnorm;                      // :87
+    try {
+        std::vector<double> hist;
+        LKCHK(cg_impl(A, M, Bb, jb, Bx, jx, W, tol, xnorm, maxiter, hist, info));
+        if (res)
+            for (int64_t i = 0; i < res_cap && i < (int64_t)hist.size(); ++i) res[i] = hist[(size_t)i];
+        if (nres) *nres = (int64_t)hist.size();
+        return LK_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(LK_ERR_NOMEM, "lk_cg: no host memory for the residual history");
     }
 }
 

@@ -3295,6 +3295,184 @@ __global__ __launch_bounds__(256) void k_scal(double *__restrict__ x, int64_t n,
     if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[nd - 1] *= ar;
 }
 
+// ---- conjugate gradient (lk_cg; src/IterativeSolvers/CG/CG.fypp:123-171) ---------------------------------------------------------------
+// Three grid-stride passes, cg_update, cg_scalars and cg_direction below.  They are device functions that k_axpby runs INSTEAD of its own
+// loops when its last argument names one of them (CgArgs::pass, block-uniform; lk_linop_residual's branch is the precedent): they are
+// BLAS-1 passes of k_axpby's shape, launched by its grid rule, and the code object gains no kernel instance.
+// The iteration's scalars live in device memory and never reach the host on the critical path.  sc (doubles, (re, im) pairs, the
+// imaginary parts 0 for the real kind): sc[0:2] = rho = r.z of the iteration before (r_dot_r_old), sc[2:4] = p.Ap of this one,
+// sc[4:6] = beta.  The complex quotients alpha = rho / (p.Ap) (:127) and beta = rho' / rho (:157) are formed by cg_div below, the
+// division written out (Smith's form, no library call):
+//     (a + i b) / (c + i d):  |c| >= |d|:  t = d / c, s = c + d t,  ((a + b t) / s,  (b - a t) / s)
+//                             |c| <  |d|:  t = c / d, s = c t + d,  ((a t + b) / s,  (b t - a) / s)
+// which for d = 0 is a / c and b / c, the real quotient.  The real kind divides the two doubles.
+template <bool CPLX>
+__device__ __forceinline__ v2d cg_div(v2d num, v2d den) {
+    if constexpr (!CPLX) return v2d{num.x / den.x, 0.0};
+    else {
+        if (fabs(den.x) >= fabs(den.y)) {
+            const double t = den.y / den.x, s = den.x + den.y * t;
+            return v2d{(num.x + num.y * t) / s, (num.y - num.x * t) / s};
+        }
+        const double t = den.x / den.y, s = den.x * t + den.y;
+        return v2d{(num.x * t + num.y) / s, (num.y * t - num.x) / s};
+    }
+}
+// a p.Ap the iteration cannot divide by: zero, or not finite (every thread of every kernel of the iteration sees the same value)
+__device__ __forceinline__ bool cg_bad_pap(v2d q) { return !(isfinite(q.x) && isfinite(q.y)) || (q.x == 0.0 && q.y == 0.0); }
+
+// x += alpha p and r -= alpha Ap in ONE pass (:127-131), alpha = sc[0:2] / sc[2:4] formed here: four read streams, two write streams, one
+// 16-byte access per stream and lane in flight (the header's rule for axpby).  Each element as the reference's axpby forms it:
+// alpha p + 1 x, (-alpha) Ap + 1 r.  partial != NULL (block-uniform; no preconditioner): this block's share of the new r.r (:137) is formed
+// in the same pass, in k_dot's layout (partial[b], partial[pstride + b] = 0), for cg_scalars to finish.  A p.Ap of zero or not finite:
+// nothing is written (cg_scalars raises the stop flag for it).
+template <bool CPLX>
+__device__ __forceinline__ void cg_update(const double *__restrict__ sc, const double *__restrict__ p, const double *__restrict__ Ap,
+                                                   double *__restrict__ x, double *__restrict__ r, int64_t n, int nt,
+                                                   double *__restrict__ partial, int64_t pstride, Guard guard) {
+    if (stopped(guard)) return;
+    const v2d rho = v2d{sc[0], sc[1]}, q = v2d{sc[2], sc[3]};
+    if (cg_bad_pap(q)) return;
+    const v2d al = cg_div<CPLX>(rho, q), nal = -al;
+    constexpr int ED = K<CPLX>::ELEM_DOUBLES;
+    const int64_t nd = n * ED, nv = nd / 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const v2d *pv = reinterpret_cast<const v2d *>(p), *av = reinterpret_cast<const v2d *>(Ap);
+    v2d *xv = reinterpret_cast<v2d *>(x), *rv = reinterpret_cast<v2d *>(r);
+    v2d acc = v2d{0.0, 0.0};
+    auto upd = [&](v2d a, v2d s, v2d y) {     // a s + 1 y
+        v2d t;
+        if constexpr (CPLX) { t = cmul(a, s); t += cmul(v2d{1.0, 0.0}, y); }
+        else { t = s * a.x; t += y * 1.0; }
+        return t;
+    };
+    if (nt) {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+            const v2d pp = __builtin_nontemporal_load(pv + i), aa = __builtin_nontemporal_load(av + i);
+            const v2d xx = __builtin_nontemporal_load(xv + i), rr = __builtin_nontemporal_load(rv + i);
+            const v2d xn = upd(al, pp, xx), rn = upd(nal, aa, rr);
+            __builtin_nontemporal_store(xn, xv + i);
+            __builtin_nontemporal_store(rn, rv + i);
+            acc += rn * rn;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+            const v2d pp = pv[i], aa = av[i], xx = xv[i], rr = rv[i];
+            const v2d xn = upd(al, pp, xx), rn = upd(nal, aa, rr);
+            xv[i] = xn;
+            rv[i] = rn;
+            acc += rn * rn;
+        }
+    }
+    if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double xn = al.x * p[nd - 1], rn = nal.x * Ap[nd - 1];
+        xn += 1.0 * x[nd - 1];
+        rn += 1.0 * r[nd - 1];
+        x[nd - 1] = xn;
+        r[nd - 1] = rn;
+        acc.x += rn * rn;
+    }
+    if (!partial) return;
+    __shared__ double red[4];
+    const double s = wave_sum(acc.x + acc.y);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        partial[pstride + blockIdx.x] = 0.0;
+    }
+}
+
+// ONE block behind the partial sums of rho' = r.r (cg_update) or r.z (k_dot): finishes them in finish_partials' fixed order (one wave
+// per slot, lanes strided over the blocks, wave_sum), writes hist[0:2] = rho' and hist[2:4] = p.Ap (the iteration's slot of the history
+// ring), forms beta = rho' / rho into sc[4:6] (:157), raises the stop flag with THIS iteration's number when sqrt|rho'| < tol (:141-154)
+// or when rho' is not finite, and rotates rho <- rho' (:167).  A p.Ap of zero or not finite (cg_update wrote nothing, so there are no
+// sums to finish): the flag is raised, the slot gets p.Ap and a rho' of NaN, and rho and beta stay as they are.
+template <bool CPLX>
+__device__ __forceinline__ void cg_scalars(const double *__restrict__ partial, int64_t pstride, int nblocks, double *__restrict__ sc,
+                                           double *__restrict__ hist, double tol, int *__restrict__ stop_out, Guard guard) {
+    if (stopped(guard)) return;
+    const v2d q = v2d{sc[2], sc[3]};
+    if (cg_bad_pap(q)) {             // (block-uniform)
+        if (threadIdx.x == 0) {
+            hist[0] = __builtin_nan(""); hist[1] = __builtin_nan(""); hist[2] = q.x; hist[3] = q.y;
+            *stop_out = guard.step;
+        }
+        return;
+    }
+    __shared__ double sums[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < (CPLX ? 2 : 1)) {
+        const double *pp = partial + (int64_t)wave * pstride;
+        double s = 0.0;
+        for (int b = lane; b < nblocks; b += 64) s += pp[b];
+        s = wave_sum(s);
+        if (lane == 0) sums[wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const v2d rn = v2d{sums[0], CPLX ? sums[1] : 0.0}, ro = v2d{sc[0], sc[1]};
+    hist[0] = rn.x; hist[1] = rn.y; hist[2] = q.x; hist[3] = q.y;
+    const double res = sqrt(CPLX ? hypot(rn.x, rn.y) : fabs(rn.x));
+    if (!isfinite(res) || res < tol) *stop_out = guard.step;
+    const v2d be = cg_div<CPLX>(rn, ro);
+    sc[4] = be.x; sc[5] = be.y;
+    sc[0] = rn.x; sc[1] = rn.y;
+}
+
+// p = 1 z + beta p (:157-164), beta = sc[4:6] read on the device; z is r without a preconditioner.  Its guard carries the number of the
+// iteration it OPENS: after a stop in iteration i it does not run, and p stays what the reference holds when it leaves the loop.
+template <bool CPLX>
+__device__ __forceinline__ void cg_direction(const double *__restrict__ sc, const double *__restrict__ z, double *__restrict__ p,
+                                                      int64_t n, int nt, Guard guard) {
+    if (stopped(guard)) return;
+    const v2d be = v2d{sc[4], sc[5]};
+    constexpr int ED = K<CPLX>::ELEM_DOUBLES;
+    const int64_t nd = n * ED, nv = nd / 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const v2d *zv = reinterpret_cast<const v2d *>(z);
+    v2d *pv = reinterpret_cast<v2d *>(p);
+    auto dir = [&](v2d zz, v2d pp) {
+        v2d t;
+        if constexpr (CPLX) { t = cmul(v2d{1.0, 0.0}, zz); t += cmul(be, pp); }
+        else { t = zz * 1.0; t += pp * be.x; }
+        return t;
+    };
+    if (nt) {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+            const v2d zz = __builtin_nontemporal_load(zv + i), pp = __builtin_nontemporal_load(pv + i);
+            __builtin_nontemporal_store(dir(zz, pp), pv + i);
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+            const v2d zz = zv[i], pp = pv[i];
+            pv[i] = dir(zz, pp);
+        }
+    }
+    if (!CPLX && (nd & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double t = 1.0 * z[nd - 1];
+        t += be.x * p[nd - 1];
+        p[nd - 1] = t;
+    }
+}
+
+// what k_axpby's last argument carries for the three passes (pass = 0: none, k_axpby itself runs)
+enum { CG_PASS_NONE = 0, CG_PASS_UPDATE = 1, CG_PASS_SCALARS = 2, CG_PASS_DIRECTION = 3 };
+struct CgArgs {
+    int pass = CG_PASS_NONE;
+    double *sc = nullptr;            // the iteration's scalars
+    const double *a = nullptr;       // update: p;  direction: z (or r)
+    const double *b = nullptr;       // update: Ap
+    double *x = nullptr;             // update: x;  direction: p
+    double *r = nullptr;             // update: r
+    double *hist = nullptr;          // scalars: the iteration's history slot
+    double tol = 0.0;                // scalars
+    int *stop_out = nullptr;         // scalars
+    int nblocks = 0;                 // scalars: partial sums to finish
+    Guard guard = Guard{nullptr, 0};
+};
+
 // inv_sqrt_of != NULL (lk_kexpm's first Krylov vector, with beta = 0): alpha = 1 / sqrt(|*inv_sqrt_of|) read on the device, as k_scal's
 // fused normalise does, but OUT OF PLACE: y = x / ||x|| with ||x||^2 left there by k_dot + finish_partials is one read and one write
 // with no host round trip (the reference's `zero_basis; X(1)%add(b); X(1)%scal(1 / beta)`, ExpmLib.fypp:186-187, is two of each behind
@@ -3310,7 +3488,13 @@ template <bool CPLX>
 __global__ __launch_bounds__(256) void k_axpby(double ar, double ai, const double *__restrict__ x, double br,
                                                double bi, double *__restrict__ y, int64_t n, int nt,
                                                const double *__restrict__ inv_sqrt_of, double *__restrict__ partial = nullptr,
-                                               int64_t pstride = 0) {
+                                               int64_t pstride = 0, CgArgs cg = CgArgs{}) {
+    if (cg.pass != CG_PASS_NONE) {   // lk_cg's passes (above): ar, ai, x, br, bi, y, inv_sqrt_of are not read
+        if (cg.pass == CG_PASS_UPDATE) cg_update<CPLX>(cg.sc, cg.a, cg.b, cg.x, cg.r, n, nt, partial, pstride, cg.guard);
+        else if (cg.pass == CG_PASS_SCALARS) cg_scalars<CPLX>(partial, pstride, cg.nblocks, cg.sc, cg.hist, cg.tol, cg.stop_out, cg.guard);
+        else cg_direction<CPLX>(cg.sc, cg.a, cg.x, n, nt, cg.guard);
+        return;
+    }
     if (partial) {
         constexpr int ED = K<CPLX>::ELEM_DOUBLES;
         const int64_t nd = n * ED, nv = nd / 2;

@@ -561,12 +561,42 @@ def eigs(A: abstract_linop, X, x0: abstract_vector | None = None, kdim: int | No
 # ------------------------------------------------------------------------------------------
 # The other solver families of the reference: callers of the same primitives, restated for completeness of the
 # host-side mirror (through the Fortran plugin the reference's own drivers run unchanged).
+def _cg_engine(A, b, x, rtol, atol, M, maxiter, meta) -> int:
+    """cg as ONE engine call (lk_cg): alpha and beta are formed on the device, the host reads the residual history in deliveries."""
+    import ctypes as C
+    from . import _capi
+    W = krylov_basis_gpu(b.basis.n_local, 4 if M is not None else 3, b.dtype, b.basis.ctx)
+    cap = maxiter + 1
+    res = np.zeros(max(cap, 1))
+    nres, info = C.c_int64(), C.c_int()
+    A.reset_counter(False, "cg%init")
+    _capi.check(W._lib.lk_cg(A._h, M._h if M is not None else None, b.basis._h, b.col, x.basis._h, x.col, W._h, float(rtol), float(atol),
+                             maxiter, res.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(nres), C.byref(info)))
+    if meta is not None:
+        meta.n_iter = abs(info.value)
+        meta.res = [float(r) for r in res[:nres.value]]
+        # info = 0 with maxiter > 0: a start residual of exactly zero (nres = 1, res[0] = 0), x solves the system as it came
+        meta.converged, meta.info = info.value > 0 or (info.value == 0 and maxiter > 0), info.value
+    A.reset_counter(False, "cg%post")
+    return info.value
+
+
 def cg(A: abstract_linop, b: abstract_vector, x: abstract_vector, rtol: float = rtol_dp, atol: float = atol_dp,
-       preconditioner=None, options: cg_dp_opts | None = None, meta: cg_dp_metadata | None = None) -> int:
+       preconditioner=None, options: cg_dp_opts | None = None, meta: cg_dp_metadata | None = None, engine: bool | None = None) -> int:
     """Conjugate gradient for symmetric / Hermitian positive definite operators.
     src/IterativeSolvers/CG/CG.fypp:98-200.  x is the initial guess and is overwritten by the solution.
-    Returns info = +n_iter if converged, -n_iter otherwise."""
+    Returns info = +n_iter if converged, -n_iter otherwise.
+    `engine` (engine extra): True runs the whole solve as one lk_cg call and raises TypeError unless A is an engine operator, the
+    vectors are GPU vectors, the preconditioner is None or a `linop_precond_gpu` and the context has one rank; a start residual of
+    exactly zero then returns info = 0 with `meta.converged`, the history [0.0] and x untouched (the reference divides by it, :127).
+    False and None keep the loop below."""
     opts = options or cg_dp_opts()
+    if engine:
+        able = (isinstance(A, _engine_linop) and isinstance(b, dense_vector_gpu) and isinstance(x, dense_vector_gpu)
+                and (preconditioner is None or isinstance(preconditioner, linop_precond_gpu)) and b.basis.ctx.nranks == 1)
+        if not able:
+            raise TypeError("cg(engine=True) needs an engine operator, GPU vectors, no preconditioner or a linop_precond_gpu, and one rank")
+        return _cg_engine(A, b, x, rtol, atol, preconditioner.M if preconditioner is not None else None, opts.maxiter, meta)
     tol = atol + rtol * b.norm()                                                   # :110
     r, p, Ap = b.zeros_like(), b.zeros_like(), b.zeros_like()                      # allocate(..., mold=b); zero()   :113-121
     m = cg_dp_metadata()

@@ -299,6 +299,12 @@ int lk_gmres(void *A, int trans, void *M, void *Bb, int jb, void *Bx, int jx, vo
     (void)res; (void)res_cap; (void)nres; (void)n_inner; (void)n_outer; (void)info;
     return fail("lk_gmres is not in the mock");
 }
+int lk_cg(void *A, void *M, void *Bb, int jb, void *Bx, int jx, void *W, double rtol, double atol, int maxiter, double *res, int64_t res_cap,
+          int64_t *nres, int *info) {
+    (void)A; (void)M; (void)Bb; (void)jb; (void)Bx; (void)jx; (void)W; (void)rtol; (void)atol; (void)maxiter; (void)res; (void)res_cap; (void)nres;
+    (void)info;
+    return fail("lk_cg is not in the mock");
+}
 int lk_comm_get_unique_id(void *id) { memset(id, 0, 128); return LK_OK; }
 int lk_comm_init_rank(mock_ctx *c, int nranks, int rank, const void *id) { (void)c; (void)rank; (void)id; return nranks == 1 ? LK_OK : fail("no collective in the mock"); }
 int lk_comm_info(mock_ctx *c, int *nranks, int *rank) { (void)c; if (nranks) *nranks = 1; if (rank) *rank = 0; return LK_OK; }
